@@ -7,6 +7,12 @@ actions already resident in HBM.  Workload = BASELINE.json configs[1]:
 GPU (torchrun), envs sharded with no data-path collective (weak scaling);
 the MAX elapsed time over ranks is used.
 
+A plain run sets up, warms up, times --steps steps, writes the last timed step's
+outputs if --dump-outputs DIR is given, and prints the line.  --full adds what
+the headline figure does not need: the CPU leg (live FLOP count of the timed mix,
+one-step parity against the fp64 oracle, CPU baselines) and the comparison run
+with one launch per step ('per_step').
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -81,6 +87,29 @@ def launch_chunks(count: int, m: int, pool_slots: int) -> list:
         out.append(min(m, count - j, pool_slots - j % pool_slots))
         j += out[-1]
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, arrays: dict, rank: int = 0, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """--dump-outputs: `arrays` (name -> array whose first axis is the env) as out_dir/<name>.npy in
+    float32 (rank r > 0 of a multi-rank run: <name>.rank<r>.npy).  Past `limit` bytes in all, the same
+    fixed, seeded sample of env rows (ascending env ids) of every array -> {name: shape written}."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32) for k, a in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(n, 1) for a in arrays.values())
+    limit -= 1024 * len(arrays)  # the .npy headers
+    if n * row_bytes > limit:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=max(1, limit // row_bytes), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(out_dir / (f"{k}.npy" if rank == 0 else f"{k}.rank{rank}.npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def bench_fields(env, terrain: str, n_fields: int = 4):
@@ -255,12 +284,22 @@ def main() -> None:
     ap.add_argument("--action-pool", type=int, default=512,
                     help="steps of random actions resident in HBM ([P][n][3], reused cyclically); a launch never "
                          "crosses the pool's end")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU leg (live FLOP count of the timed "
+                         "mix, parity probe, CPU baselines) and the one-launch-per-step comparison run.  Without it "
+                         "the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (obs, reward, done, terminal_obs, pos2d of every "
+                         "env) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU leg")
     ap.add_argument("--no-per-step", action="store_true",
-                    help="skip the one-launch-per-step comparison run (profiler counter passes)")
+                    help="with --full: skip the one-launch-per-step comparison run (profiler counter passes)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--traffic-json", default=str(ROOT / "profiles" / "traffic.json"))
     args = ap.parse_args()
+    # a plain run does what the headline figure needs; the CPU leg and the comparison run are --full's
+    cpu_leg = args.full and not args.no_cpu_baseline
+    per_step_run = args.full and not args.no_per_step
 
     import torch
     import torch.distributed as dist
@@ -363,6 +402,15 @@ def main() -> None:
         gc.enable()
         step_ms = ev0.elapsed_time(ev1) / args.steps  # whole step sequence per step, torch's stream
         st1 = env.stats()
+        if args.dump_outputs:  # what the window's last step returned, before anything steps the envs again
+            if m:
+                last = chunks(args.steps, m)[-1] - 1
+                outs = {"obs": mo[last], "reward": mr[last], "done": md[last], "terminal_obs": mt[last],
+                        "pos2d": mp[last]}
+            else:
+                outs = {"obs": env.obs, "reward": env.reward, "done": env.done, "terminal_obs": env.terminal_obs,
+                        "pos2d": env.pos2d}
+            timed.outputs = {k: t.cpu().numpy() for k, t in outs.items()}
         if graph is not None:  # graph replays carry no per-kernel events: time eager steps of the same kernels
             env.time_kernel(min(args.steps, 100))
             for i in range(min(args.steps, 100)):
@@ -375,8 +423,9 @@ def main() -> None:
 
     run(args.burn_in + args.warmup, M)
     # the CPU leg's FLOP count replays the timed window's own mix: snapshot it before the window
-    mix = mix_snapshot(env, pool, args.steps) if (world == 1 and not args.no_cpu_baseline) else None
+    mix = mix_snapshot(env, pool, args.steps) if (world == 1 and cpu_leg) else None
     elapsed, step_ms, ktimes, kern_n, st0, st1 = timed(M)
+    dumped = dump_outputs(args.dump_outputs, timed.outputs, rank) if args.dump_outputs else None
     enqueue_ms = {"all": timed.enqueue_ms, "torch_event_record": timed.event_record_ms}  # (timed() runs again below)
     pair = env.pair_counters() if (M and env.relief) else None  # the last timed launch (relief pair)
     if pair is not None and pair["claims_fast"] + pair["claims_full"] > 0:
@@ -394,7 +443,7 @@ def main() -> None:
         # the launch is its slowest env's chain: how far the slowest env is from the median one
         pair["chain_p100_over_p50"] = pair["env_mcycles"]["p100"] / max(pair["env_mcycles"]["p50"], 1e-9)
     per_step = None
-    if M and not args.no_per_step:  # the same steps with one bb_step launch per step (what a closed-loop rollout uses)
+    if M and per_step_run:  # the same steps with one bb_step launch per step (what a closed-loop rollout uses)
         run(args.warmup, 0)
         per_step = timed(0)
     stats = env.stats()
@@ -540,7 +589,10 @@ def main() -> None:
                 "step_ms_hip_events": pms, "kernel_ms_all": pk, "kernel_launches_timed": pn,
                 "note": "the same steps with one bb_step launch per step, the form a closed-loop (policy) rollout "
                         "uses: every step waits for the slowest env of the GPU"}
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            line["outputs"] = {"dir": str(args.dump_outputs), "arrays": dumped, "dtype": "float32",
+                               "what": "the last timed step's outputs, one row per env"}
+        if world == 1 and cpu_leg:
             if args.terrain == "flat":
                 line["parity"] = parity_probe(env)
             fields, desc = bench_fields(env, args.terrain)

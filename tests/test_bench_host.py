@@ -52,6 +52,32 @@ def test_launch_chunks_driver_window_is_one_launch():
     assert bench.launch_chunks(500, 256, 256) == [256, 244]
 
 
+def test_dump_outputs_writes_float32_and_samples_past_the_limit(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32, whole below the byte limit; past it
+    the same seeded sample of env rows (ascending) of every array, the same from call to call."""
+    import numpy as np
+
+    n = 100
+    arrays = {"obs": np.arange(n * 15, dtype=np.float64).reshape(n, 15),
+              "done": (np.arange(n) % 3 == 0).astype(np.uint8)}
+    shapes = bench.dump_outputs(tmp_path / "all", arrays)
+    assert shapes == {"obs": [n, 15], "done": [n]}
+    obs, done = np.load(tmp_path / "all" / "obs.npy"), np.load(tmp_path / "all" / "done.npy")
+    assert obs.dtype == np.float32 and done.dtype == np.float32
+    assert np.array_equal(obs, arrays["obs"]) and np.array_equal(done, arrays["done"])
+    limit = 2 * 1024 + 10 * 64  # headers + ten 64-byte rows
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(tmp_path / d, arrays, limit=limit) == {"obs": [10, 15], "done": [10]}
+    s1, s2 = np.load(tmp_path / "s1" / "obs.npy"), np.load(tmp_path / "s2" / "obs.npy")
+    assert np.array_equal(s1, s2)
+    rows = (s1[:, 0] / 15).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, arrays["obs"][rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "done.npy"), arrays["done"][rows])
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) <= limit
+    bench.dump_outputs(tmp_path / "r", arrays, rank=1)
+    assert (tmp_path / "r" / "obs.rank1.npy").exists()
+
+
 def test_committed_flops_and_profiles_name_their_basis():
     """Lines without the CPU leg (N > 1 ranks, --no-cpu-baseline) take the committed FLOP count of
     their terrain, on the same yardstick as the live count (bench.FLOP_BASIS); the same-shape

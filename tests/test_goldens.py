@@ -21,7 +21,7 @@ def _meta(name):
 def test_terrain_generators_match_reference(case):
     import ballbot_gym.terrain as T
 
-    ref = np.load(GOLD / "terrains.npz")[case["key"]]
+    ref = np.load(GOLD / case["file"])[case["key"]]
     out = T.BUILTIN_TERRAINS[case["type"]](case["n"], **json.loads(json.dumps(case["config"])))
     assert out.shape == (case["n"] ** 2,) and out.dtype == np.float64
     np.testing.assert_array_equal(out, ref)

@@ -14,7 +14,7 @@ mkdir -p $O
 STEPS=${STEPS:-"envs32k_flat envs32k_perlin ranks8_gloo ppo32k"}
 for s in $STEPS; do
   case $s in
-    envs32k_flat)   timeout -k 10 300 python -u bench.py --envs 32768 --steps 200 --warmup 100 --no-per-step --cpu-seconds 4 > $O/$s.json 2> $O/$s.log || { tail -5 $O/$s.log; exit 1; } ;;
+    envs32k_flat)   timeout -k 10 300 python -u bench.py --full --envs 32768 --steps 200 --warmup 100 --no-per-step --cpu-seconds 4 > $O/$s.json 2> $O/$s.log || { tail -5 $O/$s.log; exit 1; } ;;
     envs32k_perlin) timeout -k 10 300 python -u bench.py --envs 32768 --terrain perlin --steps 200 --warmup 100 --no-per-step --no-cpu-baseline > $O/$s.json 2> $O/$s.log || { tail -5 $O/$s.log; exit 1; } ;;
     ranks8_gloo)    BB_BENCH_BACKEND=gloo OMP_NUM_THREADS=2 timeout -k 10 400 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
                       --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 8 --steps 20 --warmup 5 --no-cpu-baseline --no-per-step \

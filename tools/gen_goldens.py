@@ -11,7 +11,8 @@ data (inputs + expected outputs); no reference source travels.
 
 What is pinned (consumers in tests/test_goldens.py):
   terrains.npz   every numpy terrain generator at n=33/65 (default and varied
-                 configs) + hills/sinusoidal at n=293, float64
+                 configs), float64; hills/sinusoidal at n=293 in
+                 terrains293_<type>.npz (terrains.json names each case's file)
   rewards.npz    DirectionalReward / DistanceReward on random states
   pid.npz        PID.act trajectories on random rotations (torch)
   seeds.json     gymnasium np_random streams (PCG64(SeedSequence(seed)))
@@ -107,7 +108,11 @@ def gen_terrains():
         meta.append({"key": key, "type": "hills", "n": 293, "config": {"seed": seed}})
     out["sinusoidal293"] = np.asarray(sinus.generate_sinusoidal_terrain(293), np.float64)
     meta.append({"key": "sinusoidal293", "type": "sinusoidal", "n": 293, "config": {}})
-    np.savez_compressed(OUT / "terrains.npz", **out)
+    # one file for the small grids and one per generator for n=293: every file stays below 1 MiB
+    for m in meta:
+        m["file"] = "terrains.npz" if m["n"] != 293 else f"terrains293_{m['type']}.npz"
+    for f in sorted({m["file"] for m in meta}):
+        np.savez_compressed(OUT / f, **{m["key"]: out[m["key"]] for m in meta if m["file"] == f})
     (OUT / "terrains.json").write_text(json.dumps(meta, indent=1))
 
 

@@ -48,11 +48,11 @@ for s in $STEPS; do
            tail -1 $O/tests.log ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
            tail -1 $O/smoke.log ;;
-    flat)   bench flat 400 ;;
-    driver) bench driver 300 --steps 20 --warmup 5 ;;
-    perlin) bench perlin 400 --terrain perlin ;;
-    hills)  bench hills 300 --terrain hills --no-cpu-baseline ;;
-    fp32)   bench fp32 300 --precision fp32 --no-cpu-baseline ;;
+    flat)   bench flat 400 --full ;;
+    driver) bench driver 300 --full --steps 20 --warmup 5 ;;
+    perlin) bench perlin 400 --full --terrain perlin ;;
+    hills)  bench hills 300 --full --terrain hills --no-cpu-baseline ;;
+    fp32)   bench fp32 300 --full --precision fp32 --no-cpu-baseline ;;
     prof_flat)
       prof prof_flat multi NAME=flat ARGS="--terrain flat"
       python tools/prof_summary.py gpurun_out/prof_${TAG}_flat profiles/${TAG}_flat_multi --kernel multi --f64 --traffic > $O/sum_flat.log 2>&1 || { tail $O/sum_flat.log; exit 1; }
