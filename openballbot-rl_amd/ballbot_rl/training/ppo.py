@@ -339,7 +339,7 @@ class _UpdateGraphs:
 
         opt, lib = ppo.optimizer, N.lib()
         nbytes = C.c_int64()
-        N.check(lib.bb_ppo_mlp_workspace_bytes(int(ppo.batch_size), C.byref(nbytes)), "bb_ppo_mlp_workspace_bytes")
+        N.check(lib.bb_ppo_mlp_workspace_bytes(int(self.B), C.byref(nbytes)), "bb_ppo_mlp_workspace_bytes")
         self.ws = torch.empty(int(nbytes.value) // 4, device=ppo.device)
         a = N.PPOMlpArgs()
         a.params, a.grad, a.exp_avg, a.exp_avg_sq = (t.data_ptr() for t in (opt.flat, opt.grad, opt.exp_avg,

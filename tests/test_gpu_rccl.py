@@ -178,3 +178,26 @@ def test_dp_local_minibatch_below_256_takes_the_autograd_graph(monkeypatch):
     assert g is not None and g.dp and not g.fused and g.B == 128
     log = g.run(m, {k: v.clone() for k, v in d.items()}, 0.2)
     assert log.shape == (2 * n // 128, 6) and np.isfinite(log).all()
+
+
+def test_dp_fused_workspace_is_sized_by_the_local_minibatch():
+    """the fused data-parallel step sizes its workspace from the LOCAL minibatch.  The
+    global batch_size 32768 is outside bb_ppo_mlp_workspace_bytes' range (256..16384); a local
+    minibatch of 4096 rows (eight ranks) is fused, so its graphs must build and run."""
+    from test_gpu_ppo import _gpu_fake
+
+    from ballbot_rl.training.logger import CSVLogger
+    from ballbot_rl.training.ppo import BatchedPPO, fused_mlp_slots
+
+    m = BatchedPPO(_gpu_fake(), n_steps=16, batch_size=32768, n_epochs=2, seed=4, update_mode="allreduce",
+                   logger=CSVLogger(None, stdout=False))
+    m._force_dp = True
+    assert fused_mlp_slots(m) is None and fused_mlp_slots(m, B=4096) is not None
+    m.collect_rollouts()
+    d = m.buf.flat()
+    n = d["obs"].shape[0]
+    assert n == 4096
+    g = m._graphs_for(n, 4096)
+    assert g is not None and g.dp and g.fused and g.B == 4096
+    log = g.run(m, {k: v.clone() for k, v in d.items()}, 0.2)
+    assert log.shape == (2 * n // 4096, 6) and np.isfinite(log).all()
