@@ -2508,7 +2508,7 @@ int bb_render_depth(bb_handle* h, float* depth, float* rel_ts, int height, int w
   HIPCHK(hipSetDevice(h->device));
   RenderDev rd{h->n, h->d.qpos, h->d.steps, h->d.terrain, h->bank, h->size_z, h->hmax};
   if (!h->scenes) HIPCHK(hipMalloc(&h->scenes, scene_bytes(h->n)));
-  if (launch_depth(h->fp64 != 0, h->mf, h->rig, rd, height, width, every, force, float(h->md.h), h->scenes, depth, rel_ts,
+  if (launch_depth(h->fp64 != 0, h->mf, h->rig, rd, height, width, every, force, double(h->md.h), h->scenes, depth, rel_ts,
                    (hipStream_t)stream))
     return fail("bb_render_depth: launch failed: %s", hipGetErrorString(hipGetLastError()));
   return 0;

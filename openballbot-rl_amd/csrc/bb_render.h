@@ -27,6 +27,6 @@ struct RenderDev {
 // scratch the launch needs: per (env, camera) scene
 size_t scene_bytes(int n);
 int launch_depth(bool fp64, const ModelT<float>& m, const CamRig& rig, const RenderDev& d, int H, int W, int every,
-                 int force, float dt, void* scenes, float* depth, float* rel_ts, hipStream_t s);
+                 int force, double dt, void* scenes, float* depth, float* rel_ts, hipStream_t s);
 
 }  // namespace bb

@@ -87,6 +87,13 @@ __device__ float ray_cylinder(const float* o, const float* d, const float* pa, c
   return fminf(t0, t1);
 }
 
+// Two-sided Moller-Trumbore.  The barycentric tests accept TRI_PAD (of a cell, 3.4 um) outside the
+// triangle: in float u and v carry ~1e-5 of rounding (|o - a| / cell * 2^-24, the hit point's own
+// rounding at |x| = 5), so with exact tests 4 rays in 10^6 slipped between the two triangles of a
+// cell or two cells and came back as depth 1.  The overlap moves a hit by the change of slope across
+// the edge times 3.4 um at most.
+constexpr float TRI_PAD = 1e-4f;
+
 __device__ float ray_tri(const float* o, const float* d, const float* a, const float* b, const float* c) {
   const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
   const float p[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
@@ -95,10 +102,10 @@ __device__ float ray_tri(const float* o, const float* d, const float* a, const f
   const float inv = 1.f / det;
   const float s[3] = {o[0] - a[0], o[1] - a[1], o[2] - a[2]};
   const float u = dot3(s, p) * inv;
-  if (u < 0.f || u > 1.f) return -1.f;
+  if (u < -TRI_PAD || u > 1.f + TRI_PAD) return -1.f;
   const float q[3] = {s[1] * e1[2] - s[2] * e1[1], s[2] * e1[0] - s[0] * e1[2], s[0] * e1[1] - s[1] * e1[0]};
   const float v = dot3(d, q) * inv;
-  if (v < 0.f || u + v > 1.f) return -1.f;
+  if (v < -TRI_PAD || u + v > 1.f + TRI_PAD) return -1.f;
   return dot3(e2, q) * inv;
 }
 
@@ -108,10 +115,12 @@ __device__ float ray_hfield(const float* o, const float* d, const float* hf, flo
   const int N1 = HF_N - 1;
   const float dx = 2.f * sx / N1, dy = 2.f * sy / N1;
   float t0 = tmin, t1 = tmax;
-  // no surface above ztop: start where the ray descends through it (flat: the plane hit)
+  // no surface above ztop: start 1 mm before the ray descends through it (flat: the plane hit).
+  // The margin is absolute: the start point rounds by up to 5e-7 m at |x| = 5, and a start cell
+  // past the hit's cell is a hole.
   if (o[2] > ztop) {
     if (d[2] >= 0.f) return -1.f;
-    t0 = fmaxf(t0, (ztop - o[2]) / d[2] * (1.f - 1e-6f));
+    t0 = fmaxf(t0, (ztop - o[2]) / d[2] - 1e-3f);
   }
   const float half[2] = {sx, sy};
 #pragma unroll
@@ -166,11 +175,11 @@ __device__ void to_world(const Kin<float>& k, const float* pl, float* pw) {
 // one thread per env: camera frames and primitives of both cameras -> scenes[e][cam]
 template <typename T>
 __global__ __launch_bounds__(64) void scene_kernel(ModelT<float> m, CamRig rig, RenderDev d, int every, int force,
-                                                   float dt, Scene* __restrict__ scenes, float* __restrict__ rel_ts) {
+                                                   double dt, Scene* __restrict__ scenes, float* __restrict__ rel_ts) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= d.n) return;
   const int k6 = d.steps[e] % every;
-  if (rel_ts) rel_ts[e] = float(double(k6) * double(dt));
+  if (rel_ts) rel_ts[e] = float(double(k6) * dt);  // the reference subtracts two double times, then casts
   if (!force && k6 != 0) return;
   const T* Q = (const T*)d.qpos;
   float q[NQ];
@@ -257,7 +266,7 @@ __global__ __launch_bounds__(256) void depth_kernel(ModelT<float> m, RenderDev d
 size_t scene_bytes(int n) { return sizeof(Scene) * 2 * size_t(n); }
 
 int launch_depth(bool fp64, const ModelT<float>& m, const CamRig& rig, const RenderDev& d, int H, int W, int every,
-                 int force, float dt, void* scenes, float* depth, float* rel_ts, hipStream_t s) {
+                 int force, double dt, void* scenes, float* depth, float* rel_ts, hipStream_t s) {
   if (d.n <= 0) return 0;
   Scene* sc = (Scene*)scenes;
   if (fp64)

@@ -2023,21 +2023,42 @@ static double ray_hfield(const double* o, const double* d, const float* hf, doub
   return -1;
 }
 
-/* camera frames in their bodies (ballbot.xml:47,53: pos 0, euler 180 0 0) */
-void bbo_render_depth(const double* qpos, const float* hf, double size_z, int cam, int H, int W, float* out) {
+/* what cam sees at qpos: the camera frame (in its body, ballbot.xml:47,53: pos 0,
+ * euler 180 0 0), the ball centre and the six convex geoms of the base tree */
+static void render_scene(const double* qpos, int cam, double o[3], double R[9], double ball[3], Convex g[6],
+                         int cyl[6]) {
   double xpos[NB][3], xquat[NB][4], xmat[NB][9], xipos[NB][3], xI[NB][9], xanchor[3][3], xaxis[3][3];
+  compile_model();
   kinematics_all(qpos, xpos, xquat, xmat, xipos, xI, xanchor, xaxis);
-  int b = 2 + cam;
-  double qc[4], cq[4], R[9];
+  int b = 2 + cam, body[6];
+  double qc[4], cq[4], t[3];
   euler2quat(qc, 180, 0, 0);
   qmul(cq, xquat[b], qc);
   q2mat(R, cq);
-  const double* o = xpos[b];
-  Convex g[6]; int cyl[6], body[6];
+  v3copy(o, xpos[b]);
   body_geoms(xpos, xmat, g, cyl, body);
-  double ball[3], t[3];
   m3v(t, xmat[7], BALL_GPOS);
   v3add(ball, xpos[7], t);
+}
+
+void bbo_render_scene(const double* qpos, int cam, double* out) {
+  double o[3], R[9], ball[3];
+  Convex g[6]; int cyl[6];
+  render_scene(qpos, cam, o, R, ball, g, cyl);
+  memcpy(out, o, sizeof o); memcpy(out + 3, R, sizeof R); memcpy(out + 12, ball, sizeof ball);
+  out[15] = BALL_R;
+  for (int k = 0; k < 6; k++) {
+    double* s = out + 16 + 8 * k;
+    for (int q = 0; q < 3; q++) { s[q] = g[k].c[q] - g[k].a[q] * g[k].hh; s[3 + q] = g[k].c[q] + g[k].a[q] * g[k].hh; }
+    s[6] = g[k].r; s[7] = cyl[k];
+  }
+  out[64] = HF_SIZE[0]; out[65] = HF_SIZE[1];
+}
+
+void bbo_render_depth(const double* qpos, const float* hf, double size_z, int cam, int H, int W, float* out) {
+  double o[3], R[9], ball[3];
+  Convex g[6]; int cyl[6];
+  render_scene(qpos, cam, o, R, ball, g, cyl);
   const double tanh_ = 1.0; /* tan(fovy / 2), fovy 90 */
   for (int i = 0; i < H; i++)
     for (int j = 0; j < W; j++) {

@@ -137,6 +137,14 @@ void bbo_quat_to_rotvec(const double* q, double* rv);
  * (sensors/rgbd.py:46-82 over ballbot.xml:44-54; see bb_oracle.c). */
 void bbo_render_depth(const double* qpos, const float* hfield, double size_z, int cam, int H, int W, float* out);
 
+/* The scene bbo_render_depth casts its rays at, for an independent ray caster
+ * (tests/render_ref.py): out[66] = camera origin [0..3), camera->world rotation,
+ * row-major [3..12), ball centre [12..15), ball radius [15], six segments of 8
+ * from [16] (0 tower, 1-2 cam sticks, 3-5 wheels: end a[3], end b[3], radius,
+ * kind 1 cylinder / 0 capsule), hfield half extents x, y [64..66). */
+#define BBO_SCENE_N 66
+void bbo_render_scene(const double* qpos, int cam, double* out);
+
 /* Batch helper: n envs stepped sequentially on one thread (CPU baseline). */
 int bbo_env_step_batch(const bbo_env_cfg* cfg, int n, double* qpos, double* qvel,
                        double* warm, int* step_counter, const float* actions,

@@ -104,6 +104,7 @@ def lib():
         L.bbo_env_step_batch_mt.argtypes = L.bbo_env_step_batch.argtypes + [C.c_int]
         L.bbo_env_step_batch_mt.restype = C.c_int
         L.bbo_render_depth.argtypes = [dp, fp, C.c_double, C.c_int, C.c_int, C.c_int, fp]
+        L.bbo_render_scene.argtypes = [dp, C.c_int, dp]
         L.bbo_set_timestep.argtypes = [C.c_double]
         L.bbo_momentum.argtypes = [dp, dp, dp]
         _lib = L
@@ -143,6 +144,16 @@ def render_depth(qpos: np.ndarray, hfield: np.ndarray, cam: int, H: int = 64, W:
     q = np.ascontiguousarray(qpos, np.float64)
     lib().bbo_render_depth(_d(q), _f(np.ascontiguousarray(hfield, np.float32)), float(size_z), int(cam), H, W, _f(out))
     return out
+
+
+def render_scene(qpos: np.ndarray, cam: int) -> dict:
+    """What cam 0/1 sees at qpos (bbo_render_scene): the input of tests/render_ref.py."""
+    out = np.zeros(66)
+    lib().bbo_render_scene(_d(np.ascontiguousarray(qpos, np.float64)), int(cam), _d(out))
+    seg = out[16:64].reshape(6, 8)
+    return {"o": out[0:3].copy(), "R": out[3:12].reshape(3, 3).copy(), "ball": out[12:15].copy(),
+            "ball_r": float(out[15]), "pa": seg[:, 0:3].copy(), "pb": seg[:, 3:6].copy(), "rad": seg[:, 6].copy(),
+            "cyl": seg[:, 7] > 0.5, "half": (float(out[64]), float(out[65]))}
 
 
 def set_flags(flags: int) -> None:
