@@ -373,7 +373,8 @@ __global__ __launch_bounds__(64) void step_kernel(ModelT<T> mg, EnvCfg cfg, Dev 
   float o[15], r, p2[2];
   int iters = 0;
   const TerrainRef<T> tr{hf, T(d.size_z[tid]), T(d.hmax[tid]) * T(d.size_z[tid])};
-  int fl = env_step<T, BODY>(m, cfg, q, v, w, step, a, tr, W, o, r, p2, &iters, tm);
+  // the fast kernel takes the fused solve (FUSE, bb_team16.h): it has the registers for it
+  int fl = env_step<T, BODY, !BODY>(m, cfg, q, v, w, step, a, tr, W, o, r, p2, &iters, tm);
   if (!BODY && (fl & F_SLOWPATH)) {
     if (lead) {
       const int at = atomicAdd(d.slow_count + 2, 1);
@@ -482,7 +483,7 @@ __device__ __forceinline__ void out_st(V* p, V v) {
 #endif
 }
 
-template <typename T, bool HO = true, bool FULLONLY = false>
+template <typename T, bool HO = true, bool FULLONLY = false, bool FUSE = false>
 __device__ __forceinline__ int team_step(const ModelT<T>& m, const EnvCfg& cfg, const Dev& d, int e, int& tid,
                                          T* q, T* v, T* w, int& step, T* bk, const float* a, EnvWork<T>& W, float* o,
                                          float& r, float* tobs_row, float* p2_row, int auto_reset, const Team& tm,
@@ -506,7 +507,7 @@ __device__ __forceinline__ int team_step(const ModelT<T>& m, const EnvCfg& cfg, 
   fl = F_SLOWPATH;
 #else
   if constexpr (FULLONLY) fl = F_SLOWPATH;
-  else fl = full ? F_SLOWPATH : env_step<T, false>(m, cfg, q, v, w, step, a, tr, W, o, r, p2, &iters, tm);
+  else fl = full ? F_SLOWPATH : env_step<T, false, FUSE>(m, cfg, q, v, w, step, a, tr, W, o, r, p2, &iters, tm);
 #endif
   const bool slow = (fl & F_SLOWPATH) != 0;  // team-uniform
 #if BB_MULTI_MODE == 3
@@ -642,8 +643,11 @@ __global__ BB_WPE __launch_bounds__(64) void multi_step_kernel(ModelT<T> mg, Env
     const float* ak = act + 3 * row;
     const float a[3] = {ak[0], ak[1], ak[2]};
     float o[15], r;
-    const int fl = team_step<T, HO>(m, cfg, d, e, tid, q, v, w, step, bk, a, W, o, r, tobs ? tobs + 15 * row : nullptr,
-                                    pos2d ? pos2d + 2 * row : nullptr, auto_reset, tm, cnt);
+    // FUSE (bb_team16.h: the solve's broadcasts inside its FMAs) in the launch that has only the fast
+    // step compiled in: it has the registers for it; the kernels at the 512-register limit spill
+    const int fl = team_step<T, HO, false, !HO>(m, cfg, d, e, tid, q, v, w, step, bk, a, W, o, r,
+                                                tobs ? tobs + 15 * row : nullptr,
+                                                pos2d ? pos2d + 2 * row : nullptr, auto_reset, tm, cnt);
     if (!HO && (fl & F_PARKED)) {  // team-uniform
       parked = k;
       break;

@@ -26,7 +26,7 @@ struct EnvCfg {
 // mass terms, RNE forces, contacts) runs one wheel per lane, the rest of the pre-phase (kinematics, mass,
 // bias, collision) is computed redundantly by every lane of the team, the
 // constraint solve is team-parallel (bb_solve.h).
-template <typename T, bool BODY = true>
+template <typename T, bool BODY = true, bool FUSE = false>
 BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* acc, const TerrainRef<T>& tr,
                   EnvWork<T>& W, StageOut<T>* so, const Team& tm) {
   team_sync();  // previous users of the workspace are done
@@ -181,12 +181,12 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
     T acc2[NV];
 #pragma unroll
     for (int i = 0; i < NV; i++) acc2[i] = acc[i];
-    (void)t16::solve16<BODY>(m, W, ng, nb, acc2, tm.tl);
+    (void)t16::solve16<BODY, FUSE>(m, W, ng, nb, acc2, tm.tl);
     asm volatile("" ::: "memory");
     team_sync();
   }
 #endif
-  const int it = t16::solve16<BODY>(m, W, ng, nb, acc, tm.tl);
+  const int it = t16::solve16<BODY, FUSE>(m, W, ng, nb, acc, tm.tl);
 #if defined(BB_PHASE_CLOCKS)
   if (BODY && tm.tl == 0) {  // full-kernel solve cycles and Newton iterations
     atomicAdd(&bb_phase_cycles[15], clock64() - s_t0);
@@ -217,7 +217,7 @@ BB_HD bool vec_bad(const T* x, int n) {  // MuJoCo's mju_isBad over x[0..n): NaN
 // mj_checkAcc: a bad qacc after the first forward resets the data (qpos0, zero
 // velocity, warm start and ctrl; no height offset) and repeats that forward;
 // *acc_reset reports it.  ctrl is zeroed then, as mj_resetData zeroes d->ctrl.
-template <typename T, bool BODY = true>
+template <typename T, bool BODY = true, bool FUSE = false>
 BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const TerrainRef<T>& tr,
                    EnvWork<T>& W, StageOut<T>& so, const Team& tm, bool* acc_reset) {
   const T h = m.h;
@@ -271,7 +271,7 @@ BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const Terra
 #pragma unroll
       for (int i = 0; i < NV; i++) acc[i] = 2 * warm[i] - W.k1[i];
     }
-    const int fit = forward<T, BODY>(m, W.u.pre.qi, W.vi, ctrl, acc, tr, W, stage == 3 ? &so : (StageOut<T>*)nullptr, tm);
+    const int fit = forward<T, BODY, FUSE>(m, W.u.pre.qi, W.vi, ctrl, acc, tr, W, stage == 3 ? &so : (StageOut<T>*)nullptr, tm);
     if (fit < 0) return -1;  // fast path aborted (team-uniform)
     if (stage == 0 && !*acc_reset && team_any(tm, vec_bad(acc, NV))) {
       // mj_checkAcc -> mj_resetData + mj_forward (rare: stage 1 again from qpos0)
@@ -360,7 +360,7 @@ constexpr int F_TERMINATED = 1, F_FAILURE = 2, F_DIVERGED = 4, F_OVERFLOW = 8, F
 
 // One BBotSimulation.step.  obs15 = sorted keys (actions, angular_vel,
 // motor_state, orientation, vel), the order the policy's Extractor consumes.
-template <typename T, bool BODY = true>
+template <typename T, bool BODY = true, bool FUSE = false>
 BB_HD int env_step(const ModelT<T>& m, const EnvCfg& cfg, T* q, T* v, T* warm, int& step, const float* action,
                    const TerrainRef<T>& tr, EnvWork<T>& W, float* obs15, float& reward, float* pos2d,
                    int* iters, const Team& tm) {
@@ -382,7 +382,7 @@ BB_HD int env_step(const ModelT<T>& m, const EnvCfg& cfg, T* q, T* v, T* warm, i
   }
   StageOut<T>& so = W.so;  // team-shared (LDS): not register-resident across the solves
   bool acc_reset = false;
-  int it = rk4_step<T, BODY>(m, q, v, warm, ctrl, tr, W, so, tm, &acc_reset);
+  int it = rk4_step<T, BODY, FUSE>(m, q, v, warm, ctrl, tr, W, so, tm, &acc_reset);
   if (it < 0) return F_SLOWPATH;
   if (iters) *iters = it;
   if (acc_reset) flags |= F_DIVERGED;

@@ -5,22 +5,28 @@
 // (1 VALU op, no LDS round trip):
 //   team sum      row_mirror, row_half_mirror, quad_perm [2,3,0,1], [1,0,3,2]
 //                 (every lane ends with the bit-identical total)
-//   broadcast     row_newbcast:j (lane j of the row to all 16)
+//   broadcast     row_newbcast:j (lane j of the row to all 16); for doubles also inside
+//                 an FMA (fmac_bcast: v_fmac_f64_dpp)
 // Work split per Newton iteration:
 //   contact pass  lane c owns contact c (c, c+16): cone force / Hessian; its
 //                 -J'f and ground-block C-weighted J'J partials are team-summed
 //   Hessian       lane i owns ROW i of H in registers: dense M row (LDS, built
-//                 once per forward) + wheel blocks J_w' (C J)_w + ground block
+//                 once per forward) + wheel blocks J_w' (C J)_w + ground block;
+//                 a wheel block from the lane's own C J column and the other
+//                 lanes' Jacobian columns, broadcast inside the FMAs
 //   Cholesky      right-looking on the register rows; column j scaled by the
-//                 broadcast pivot, trailing update with broadcast L_kj
+//                 broadcast pivot, trailing update with L_kj broadcast inside the FMA
 //   solves        forward: column sweep with broadcasts; backward: one team
 //                 sum per unknown (lane k holds L_ki)
 //   line search   contact-parallel phi'/phi'' partials + 3 team sums
-// The arithmetic per quantity is the same as bb_solve.h:solve_team (which the
-// host tests run); only the distribution over lanes differs.
+// The arithmetic per quantity follows bb_solve.h:solve_team (which the host
+// tests run), distributed over lanes; two things differ beyond rounding-level
+// order: the pivots' reciprocal square root, and the fp64 wheel blocks, whose
+// three products per entry are accumulated one FMA at a time.
 #pragma once
 
 #include <type_traits>
+#include <utility>
 
 #include "bb_bodycon.h"
 #include "bb_solve.h"
@@ -89,12 +95,146 @@ __device__ __forceinline__ T bcast(T v) {
   return dpp<0x150 + J>(v);
 }
 
+// acc += bcast<J>(x) * own (fmac_bcast) and acc -= bcast<J>(x) * own (fnmac_bcast), one rounding.
+// For doubles the broadcast rides in the FMA itself: v_fmac_f64_dpp is the one f64 arithmetic
+// instruction gfx950 gives a DPP control (row_newbcast only), and the compiler does not fold a
+// v_mov_b64_dpp into the FMA that follows it, so it is written out.  The compiler sees no hazard
+// inside inline asm: the s_nop supplies the two wait states a DPP read needs after a VALU write of
+// the same register (x may come straight from the previous instruction).  Floats stay plain C++
+// (the f32 DPP forms are folded already).  Team-uniform control flow only, as for every pattern
+// here: a disabled source lane delivers no value.  The compiler does guard an asm's result
+// against a DPP read that follows it.  The solve takes the fused forms where its FUSE template
+// parameter asks for them (the fast step and multi-step kernels: the kernels at the 512-register
+// limit spill with the asm, bb_kernels.hip); the others keep the move + FMA pair and the LDS wheel
+// blocks, with the same bits.  -DBB_NO_FMAC_DPP turns FUSE off everywhere, for A/B builds.
+#ifndef BB_NO_FMAC_DPP
+constexpr bool kFmacDpp = true;
+#else
+constexpr bool kFmacDpp = false;
+#endif
+template <int J, typename T>
+__device__ __forceinline__ void fmac_bcast(T& acc, T x, T own) {
+#ifndef BB_NO_FMAC_DPP
+  if constexpr (sizeof(T) == 8) {
+    asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "+v"(acc)
+        : "v"(x), "v"(own), "n"(J));
+    return;
+  }
+#endif
+  acc = fma(bcast<J>(x), own, acc);
+}
+template <int J, typename T>
+__device__ __forceinline__ void fnmac_bcast(T& acc, T x, T own) {
+#ifndef BB_NO_FMAC_DPP
+  if constexpr (sizeof(T) == 8) {
+    asm("s_nop 1\n\tv_fmac_f64_dpp %0, -%1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "+v"(acc)
+        : "v"(x), "v"(own), "n"(J));
+    return;
+  }
+#endif
+  acc = fma(-bcast<J>(x), own, acc);
+}
+
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (N > 0) {
     static_for<N - 1>(f);
     f(std::integral_constant<int, N - 1>{});
   }
+}
+
+// h[J] (+|-)= bcast<J>(x) * own for every column J of a list: the same operation as fmac_bcast /
+// fnmac_bcast on each, bit for bit, but up to eight fused instructions share one hazard wait
+// (x and own are common to them, and a wait per instruction costs more than the moves it saves).
+#ifndef BB_NO_FMAC_DPP
+#define BB_FD_I(i, NEG) \
+  "v_fmac_f64_dpp %[a" #i "], " NEG "%[x], %[o] row_newbcast:%[j" #i "] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define BB_FD_A(i) [a##i] "+&v"(h[J##i])
+#define BB_FD_J(i) [j##i] "n"(J##i)
+#define BB_FD_IN [x] "v"(x), [o] "v"(own)
+#define BB_FD_CHUNK(NEG)                                                                                              \
+  if constexpr (N == 1) asm("s_nop 1\n\t" BB_FD_I(0, NEG) : BB_FD_A(0) : BB_FD_IN, BB_FD_J(0));                       \
+  if constexpr (N == 2)                                                                                               \
+    asm("s_nop 1\n\t" BB_FD_I(0, NEG) BB_FD_I(1, NEG) : BB_FD_A(0), BB_FD_A(1) : BB_FD_IN, BB_FD_J(0), BB_FD_J(1));   \
+  if constexpr (N == 3)                                                                                               \
+    asm("s_nop 1\n\t" BB_FD_I(0, NEG) BB_FD_I(1, NEG) BB_FD_I(2, NEG)                                                 \
+        : BB_FD_A(0), BB_FD_A(1), BB_FD_A(2)                                                                          \
+        : BB_FD_IN, BB_FD_J(0), BB_FD_J(1), BB_FD_J(2));                                                              \
+  if constexpr (N == 4)                                                                                               \
+    asm("s_nop 1\n\t" BB_FD_I(0, NEG) BB_FD_I(1, NEG) BB_FD_I(2, NEG) BB_FD_I(3, NEG)                                 \
+        : BB_FD_A(0), BB_FD_A(1), BB_FD_A(2), BB_FD_A(3)                                                              \
+        : BB_FD_IN, BB_FD_J(0), BB_FD_J(1), BB_FD_J(2), BB_FD_J(3));                                                  \
+  if constexpr (N == 5)                                                                                               \
+    asm("s_nop 1\n\t" BB_FD_I(0, NEG) BB_FD_I(1, NEG) BB_FD_I(2, NEG) BB_FD_I(3, NEG) BB_FD_I(4, NEG)                 \
+        : BB_FD_A(0), BB_FD_A(1), BB_FD_A(2), BB_FD_A(3), BB_FD_A(4)                                                  \
+        : BB_FD_IN, BB_FD_J(0), BB_FD_J(1), BB_FD_J(2), BB_FD_J(3), BB_FD_J(4));                                      \
+  if constexpr (N == 6)                                                                                               \
+    asm("s_nop 1\n\t" BB_FD_I(0, NEG) BB_FD_I(1, NEG) BB_FD_I(2, NEG) BB_FD_I(3, NEG) BB_FD_I(4, NEG) BB_FD_I(5, NEG) \
+        : BB_FD_A(0), BB_FD_A(1), BB_FD_A(2), BB_FD_A(3), BB_FD_A(4), BB_FD_A(5)                                      \
+        : BB_FD_IN, BB_FD_J(0), BB_FD_J(1), BB_FD_J(2), BB_FD_J(3), BB_FD_J(4), BB_FD_J(5));                          \
+  if constexpr (N == 7)                                                                                               \
+    asm("s_nop 1\n\t" BB_FD_I(0, NEG) BB_FD_I(1, NEG) BB_FD_I(2, NEG) BB_FD_I(3, NEG) BB_FD_I(4, NEG) BB_FD_I(5, NEG) \
+        BB_FD_I(6, NEG)                                                                                               \
+        : BB_FD_A(0), BB_FD_A(1), BB_FD_A(2), BB_FD_A(3), BB_FD_A(4), BB_FD_A(5), BB_FD_A(6)                          \
+        : BB_FD_IN, BB_FD_J(0), BB_FD_J(1), BB_FD_J(2), BB_FD_J(3), BB_FD_J(4), BB_FD_J(5), BB_FD_J(6));              \
+  if constexpr (N == 8)                                                                                               \
+    asm("s_nop 1\n\t" BB_FD_I(0, NEG) BB_FD_I(1, NEG) BB_FD_I(2, NEG) BB_FD_I(3, NEG) BB_FD_I(4, NEG) BB_FD_I(5, NEG) \
+        BB_FD_I(6, NEG) BB_FD_I(7, NEG)                                                                               \
+        : BB_FD_A(0), BB_FD_A(1), BB_FD_A(2), BB_FD_A(3), BB_FD_A(4), BB_FD_A(5), BB_FD_A(6), BB_FD_A(7)              \
+        : BB_FD_IN, BB_FD_J(0), BB_FD_J(1), BB_FD_J(2), BB_FD_J(3), BB_FD_J(4), BB_FD_J(5), BB_FD_J(6), BB_FD_J(7));
+// the first N of J0..J7 (distinct columns; the early clobbers keep x and own out of the
+// accumulators' registers, which later instructions of the group still read)
+template <bool NEG, int N, int J0, int J1, int J2, int J3, int J4, int J5, int J6, int J7, int M>
+__device__ __forceinline__ void fmac_chunk(double (&h)[M], double x, double own) {
+  static_assert(N >= 1 && N <= 8, "one to eight columns per hazard wait");
+  if constexpr (NEG) {
+    BB_FD_CHUNK("-")
+  } else {
+    BB_FD_CHUNK("")
+  }
+}
+#undef BB_FD_CHUNK
+#undef BB_FD_IN
+#undef BB_FD_J
+#undef BB_FD_A
+#undef BB_FD_I
+#endif
+
+template <int... J>
+constexpr int col_at(int i) {  // the list's i-th column (0 past its end)
+  constexpr int cols[] = {J...};
+  return i < int(sizeof...(J)) ? cols[i] : 0;
+}
+template <bool NEG, int OFF, int... J, typename T, int M>
+__device__ __forceinline__ void fmac_cols_from(T (&h)[M], T x, T own) {
+  constexpr int n = int(sizeof...(J)) - OFF;
+  if constexpr (n > 0) {
+#ifndef BB_NO_FMAC_DPP
+    if constexpr (sizeof(T) == 8) {
+      constexpr int c = n < 8 ? n : 8;
+      fmac_chunk<NEG, c, col_at<J...>(OFF), col_at<J...>(OFF + 1), col_at<J...>(OFF + 2), col_at<J...>(OFF + 3),
+                 col_at<J...>(OFF + 4), col_at<J...>(OFF + 5), col_at<J...>(OFF + 6), col_at<J...>(OFF + 7)>(h, x, own);
+      fmac_cols_from<NEG, OFF + 8, J...>(h, x, own);
+      return;
+    }
+#endif
+    if constexpr (OFF == 0) ((h[J] = fma(NEG ? -bcast<J>(x) : bcast<J>(x), own, h[J])), ...);
+  }
+}
+template <int... J, typename T, int M>
+__device__ __forceinline__ void fmac_bcast_cols(T (&h)[M], T x, T own) {
+  fmac_cols_from<false, 0, J...>(h, x, own);
+}
+// columns K0 .. K0 + N - 1, negated: the trailing update of a Cholesky column
+template <int K0, typename T, int M, int... I>
+__device__ __forceinline__ void fnmac_run_seq(T (&h)[M], T x, T own, std::integer_sequence<int, I...>) {
+  fmac_cols_from<true, 0, (K0 + I)...>(h, x, own);
+}
+template <int K0, int N, typename T, int M>
+__device__ __forceinline__ void fnmac_bcast_run(T (&h)[M], T x, T own) {
+  fnmac_run_seq<K0>(h, x, own, std::make_integer_sequence<int, N>{});
 }
 
 // cone_eval (bb_physics.h) without branches: the three zones are computed and
@@ -145,7 +285,7 @@ __device__ __forceinline__ T rsqrt_piv(T x) {
 // lane i holds L_ik (k < i) in h[k] and every lane holds diag[] = 1 / L_jj.
 // Entries right of a lane's diagonal (the upper triangle) are updated too,
 // without a select: they are never read, by the factorisation or the solves.
-template <typename T>
+template <bool FUSE = false, typename T>
 __device__ __forceinline__ void chol_rows(T (&h)[NV], T hdi, T (&diag)[NV], int tl) {
   static_for<NV>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
@@ -156,11 +296,15 @@ __device__ __forceinline__ void chol_rows(T (&h)[NV], T hdi, T (&diag)[NV], int 
     const T id = rsqrt_piv(piv);  // 1 / L_jj in one reciprocal square root (no sqrt + divide chain)
     diag[j] = id;  // inverse pivot: the solves multiply
     h[j] *= id;
-    static_for<NV - 1 - j>([&](auto kc) {
-      constexpr int k = j + 1 + decltype(kc)::value;
-      const T lkj = bcast<k>(h[j]);
-      h[k] -= h[j] * lkj;
-    });
+    if constexpr (FUSE && kFmacDpp) {
+      fnmac_bcast_run<j + 1, NV - 1 - j>(h, h[j], h[j]);  // h[k] -= L_kj h[j], k > j
+    } else {
+      static_for<NV - 1 - j>([&](auto kc) {
+        constexpr int k = j + 1 + decltype(kc)::value;
+        const T lkj = bcast<k>(h[j]);
+        h[k] -= h[j] * lkj;
+      });
+    }
   });
 }
 
@@ -172,16 +316,22 @@ __device__ __forceinline__ void chol_rows(T (&h)[NV], T hdi, T (&diag)[NV], int 
 //   backward  L' s = y, column sweep over L' after a transpose through LDS
 //             (scr: >= NV (NV - 1) / 2 elements of team scratch): lane k holds
 //             column k of L, so s_i needs one broadcast instead of a team sum
-template <typename T>
+template <bool FUSE = false, typename T>
 __device__ __forceinline__ void chol_solve_rows(const T (&h)[NV], const T (&diag)[NV], T gown, T (&s)[NV], T& sown,
                                                 int tl, T* scr) {
   T b = tl < NV ? -gown : T(0);
   T z = 0;  // y of this lane's row
   static_for<NV>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
-    const T yj = bcast<j>(b) * diag[j];
-    z = tl == j ? yj : z;
-    b -= h[j] * yj;  // rows <= j no longer read their right-hand side
+    if constexpr (FUSE && kFmacDpp) {
+      const T t = b * diag[j];  // lane j's is y_j (diag is replicated); the other lanes' are not read
+      z = tl == j ? t : z;
+      fnmac_bcast<j>(b, t, h[j]);  // b -= L_ij y_j; rows <= j no longer read their right-hand side
+    } else {
+      const T yj = bcast<j>(b) * diag[j];
+      z = tl == j ? yj : z;
+      b -= h[j] * yj;  // rows <= j no longer read their right-hand side
+    }
   });
   // strictly lower L, packed by rows (row i at i (i - 1) / 2)
   if (tl < NV) {
@@ -337,7 +487,7 @@ __device__ __forceinline__ void ground_get(const ModelT<T>& m, EnvWork<T>& W, in
   }
 }
 
-template <bool BODY, typename T>
+template <bool BODY, bool FUSE = false, typename T>
 __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, int tl) {
   if constexpr (!BODY) nb = 0;
   const int ngc = 3 + ng;    // wheel and ball-terrain contacts
@@ -612,39 +762,67 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
       w1 = C[3] * j0 + C[1] * j1 + C[5] * j2;
       w2 = C[4] * j0 + C[5] * j1 + C[2] * j2;
     };
+    // wheel blocks of the row: H[row][col(q)] += u' J_w[:, q] with u = C_w J_w[:, p], p the row's
+    // column in wheel w.  Doubles do without the broadcast LDS reads of the Jacobians' other
+    // columns: each lane loads only its own column j = J_w[:, p] (the gradient's 3 values per wheel,
+    // zero where the row has no column in wheel w, and then u = 0), and column q's J_w[r][q] arrives
+    // from its owner lane col(q) by row_newbcast inside the FMA: the same 13 x 3 x 3 independent
+    // products, accumulated one FMA at a time into the entry (r = 0, 1, 2).  Every lane of the team
+    // runs this (team-uniform); the column is re-read here, not held across the gradient.  Without
+    // FUSE the factors J_w[r][q] are read from LDS as before, in the same FMAs in the same order: the
+    // same bits (the multi-step launches hand envs over between kernels of both kinds).  Rows without
+    // a column skip there, under the branch the earlier code had (without it the register-limited
+    // kernels spill: 16 -> 888 B of scratch); the fused form adds J * 0 to their entries instead.
+    // That leaves an entry as it is unless it is -0, which becomes +0: the two agree bit for bit on
+    // the assumption that no mass-matrix entry of such a row is -0 (they are sums started at +0).
+    // Floats keep the earlier summation u0 J0 + u1 J1 + u2 J2, added once: there is no fused f32 instruction to gain, and
+    // the fp32 solve (Hessians conditioned ~1e10, DESIGN fp32) is held to a count of outliers that
+    // moves with the order.
+    auto wheel_blocks = [&](T (&hh)[NV]) {
+      static_for<3>([&](auto wc_) {
+        constexpr int w = decltype(wc_)::value;
+        const int p = wheel_pos(row, w);
+        const WheelCon<T>& C = W.wc[w];
+        if constexpr (sizeof(T) == 8) {
+          const int pc = p >= 0 ? p : 0;
+          const T j0 = p >= 0 ? C.J[0][pc] : T(0), j1 = p >= 0 ? C.J[1][pc] : T(0), j2 = p >= 0 ? C.J[2][pc] : T(0);
+          T u0, u1, u2;
+          cw(wCf + 9 * w, j0, j1, j2, u0, u1, u2);
+          if constexpr (FUSE && kFmacDpp) {
+            // wheel_col(0..12, w); 13 independent FMAs between two into the same entry
+            fmac_bcast_cols<0, 1, 2, 3, 4, 5, 6 + w, 9, 10, 11, 12, 13, 14>(hh, j0, u0);
+            fmac_bcast_cols<0, 1, 2, 3, 4, 5, 6 + w, 9, 10, 11, 12, 13, 14>(hh, j1, u1);
+            fmac_bcast_cols<0, 1, 2, 3, 4, 5, 6 + w, 9, 10, 11, 12, 13, 14>(hh, j2, u2);
+          } else if (p >= 0) {
+#pragma unroll
+            for (int q = 0; q < 13; q++) {
+              T& e = hh[wheel_col(q, w)];
+              e = fma(C.J[0][q], u0, e);
+              e = fma(C.J[1][q], u1, e);
+              e = fma(C.J[2][q], u2, e);
+            }
+          }
+        } else if (p >= 0) {
+          T w0, w1, w2;
+          cw(wCf + 9 * w, C.J[0][p], C.J[1][p], C.J[2][p], w0, w1, w2);
+#pragma unroll
+          for (int q = 0; q < 13; q++) hh[wheel_col(q, w)] += w0 * C.J[0][q] + w1 * C.J[1][q] + w2 * C.J[2][q];
+        }
+      });
+    };
 #ifdef BB_EXP_DUP_HESS  // timing experiment: the wheel blocks of the Hessian row twice
     {
       T h2[NV];
 #pragma unroll
       for (int k = 0; k < NV; k++) h2[k] = h[k] * T(0.5);
-      static_for<3>([&](auto wc_) {
-        constexpr int w = decltype(wc_)::value;
-        const int p = wheel_pos(row, w);
-        if (p >= 0) {
-          const WheelCon<T>& C = W.wc[w];
-          T w0, w1, w2;
-          cw(wCf + 9 * w, C.J[0][p], C.J[1][p], C.J[2][p], w0, w1, w2);
-#pragma unroll
-          for (int q = 0; q < 13; q++) h2[wheel_col(q, w)] += w0 * C.J[0][q] + w1 * C.J[1][q] + w2 * C.J[2][q];
-        }
-      });
+      wheel_blocks(h2);
       T acc = 0;
 #pragma unroll
       for (int k = 0; k < NV; k++) acc += h2[k];
       asm volatile("" :: "v"(acc) : "memory");
     }
 #endif
-    static_for<3>([&](auto wc_) {
-      constexpr int w = decltype(wc_)::value;
-      const int p = wheel_pos(row, w);
-      if (p >= 0) {
-        const WheelCon<T>& C = W.wc[w];
-        T w0, w1, w2;
-        cw(wCf + 9 * w, C.J[0][p], C.J[1][p], C.J[2][p], w0, w1, w2);
-#pragma unroll
-        for (int q = 0; q < 13; q++) h[wheel_col(q, w)] += w0 * C.J[0][q] + w1 * C.J[1][q] + w2 * C.J[2][q];
-      }
-    });
+    wheel_blocks(h);
     if (gsum) {
 #pragma unroll
       for (int ai = 0; ai < 6; ai++)
@@ -669,21 +847,21 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
       T h2[NV], d2[NV];
 #pragma unroll
       for (int k = 0; k < NV; k++) h2[k] = h[k];
-      chol_rows(h2, hdi, d2, tl);
+      chol_rows<FUSE>(h2, hdi, d2, tl);
       asm volatile("" :: "v"(d2[NV - 1]), "v"(h2[NV - 2]) : "memory");
     }
 #endif
-    chol_rows(h, hdi, diag, tl);
+    chol_rows<FUSE>(h, hdi, diag, tl);
     PH(4)
 #ifdef BB_EXP_DUP_TRSV  // timing experiment: the two triangular sweeps twice
     {
       T s2[NV], so2;
-      chol_solve_rows(h, diag, gi, s2, so2, tl, &W.u.hes.cj[0][0][0]);
+      chol_solve_rows<FUSE>(h, diag, gi, s2, so2, tl, &W.u.hes.cj[0][0][0]);
       asm volatile("" :: "v"(s2[0]), "v"(so2) : "memory");
       team_sync();
     }
 #endif
-    chol_solve_rows(h, diag, gi, s, sown, tlx, &W.u.hes.cj[0][0][0]);  // cj is dead after the Hessian
+    chol_solve_rows<FUSE>(h, diag, gi, s, sown, tlx, &W.u.hes.cj[0][0][0]);  // cj is dead after the Hessian
     T d0 = tsum(sown * gi);
     bool fin = true;
 #pragma unroll
