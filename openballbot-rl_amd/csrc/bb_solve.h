@@ -392,6 +392,7 @@ BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T*
   const int nc = 3 + ng;
   T hd[NV];  // Hessian diagonal before factorisation (pivot floor)
   int it = 0;
+  bool held = false;  // the improvement stop was overridden once (IMPR_GRAD, bb_physics.h)
   for (; it < m.maxiter; it++) {
     team_sync();
     // ---- (1) contact pass: forces and cone Hessians, contact-parallel
@@ -605,7 +606,11 @@ BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T*
     PH(6)
     if (alpha * alpha * sn <= T(1e-30) + m.step_rel2 * (1 + an2)) { it++; break; }
     // MuJoCo's improvement stop (mj_solPrimal: scale * (oldcost - cost) < tolerance)
-    if (-m.scale * dcost < m.tol) { it++; break; }
+    if (-m.scale * dcost < m.tol) {
+      const bool far = m.scale * m.scale * gn >= T(IMPR_GRAD * IMPR_GRAD) * m.tol * m.tol;
+      if (!far || held) { it++; break; }
+      held = true;
+    }
   }
   PH(7)
   PH_FLUSH(tm)

@@ -519,6 +519,7 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
 #endif
   PH_DECL
   int it = 0;
+  bool held = false;  // the improvement stop was overridden once (IMPR_GRAD, bb_physics.h)
   for (; it < m.maxiter; it++) {
     team_sync();
     PH_TOP
@@ -987,7 +988,11 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     PH(6)
     if (alpha * alpha * sn <= T(1e-30) + m.step_rel2 * (1 + an2)) { it++; break; }
     // MuJoCo's improvement stop (mj_solPrimal: scale * (oldcost - cost) < tolerance)
-    if (-m.scale * dcost < m.tol) { it++; break; }
+    if (-m.scale * dcost < m.tol) {
+      const bool far = m.scale * m.scale * gn >= T(IMPR_GRAD * IMPR_GRAD) * m.tol * m.tol;
+      if (!far || held) { it++; break; }
+      held = true;
+    }
   }
   PH(7)
 #undef BB_HROW

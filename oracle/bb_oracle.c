@@ -1187,6 +1187,16 @@ static double cone_eval(const double* jar, double mu, const double* fr, const do
   return cost;
 }
 
+/* the zone cone_eval takes for this contact: 0 top (inactive, zero force), 1 middle (sliding,
+ * force on the friction cone), 2 bottom (sticking, force strictly inside); the same predicates */
+static int cone_zone(const double* jar, double mu, const double* fr) {
+  double U0 = jar[0] * mu, U1 = jar[1] * fr[0], U2 = jar[2] * fr[1];
+  double N = U0, T = sqrt(U1 * U1 + U2 * U2);
+  if (N >= mu * T || (T <= 0 && N >= 0)) return 0;
+  if (mu * N + T <= 0 || (T <= 0 && N < 0)) return 2;
+  return 1;
+}
+
 static double total_cost(const Efc* e, const double* jar, double* force, double* Hrows /*nullable*/) {
   double cost = 0;
   for (int c = 0; c < e->nc; c++) {
@@ -1600,6 +1610,7 @@ static void forward_impl(const double* qpos, const double* qvel, const double* c
       for (int r = 0; r < 3 * nc; r++) { double s = -E.aref[r]; for (int d = 0; d < NV; d++) s += E.J[r][d] * a[d]; jar[r] = s; }
       total_cost(&E, jar, frc, NULL);
       memcpy(out->con_force, frc, 3 * nc * sizeof(double));
+      for (int c = 0; c < nc; c++) out->con_zone[c] = cone_zone(jar + 3 * c, E.mu[c], E.fr[c]);
     }
     double ek = 0;
     for (int i = 0; i < NV; i++) for (int j = 0; j < NV; j++) ek += 0.5 * qvel[i] * w->M[i * NV + j] * qvel[j];

@@ -73,6 +73,7 @@ typedef struct {
   int nbody;                    /* base-tree geom contacts (after the 3 wheel + nground ball contacts) */
   int con_body1[BBO_MAXCON];    /* 0 world (hfield), 7 ball */
   double con_force[BBO_MAXCON * 3];  /* efc_force per contact: normal, tangent 1, tangent 2 (contact frame) */
+  int con_zone[BBO_MAXCON];     /* cone_eval's zone at the solution: 0 top (inactive), 1 middle (sliding), 2 bottom (sticking) */
 } bbo_forward_out;
 
 /* Env configuration mirroring BBotSimulation.__init__ (ballbot_env.py:157-231). */

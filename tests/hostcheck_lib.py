@@ -76,7 +76,7 @@ def pair_kind_of(b, nf, ns):
 
 
 def model():
-    out = np.zeros(16)
+    out = np.zeros(23)  # hc_model writes out[0..22]
     lib().hc_model(_d(out))
     return out
 

@@ -45,6 +45,7 @@ class ForwardOut(C.Structure):
         ("nbody", C.c_int),
         ("con_body1", C.c_int * MAXCON),
         ("con_force", C.c_double * (MAXCON * 3)),
+        ("con_zone", C.c_int * MAXCON),
     ]
 
 

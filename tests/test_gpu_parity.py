@@ -3,7 +3,9 @@
 Teacher-forced: every env starts each step from the oracle's state, so the
 comparison measures one mj_step + glue, not chaotic drift.
 
-fp64 kernel (the default): qpos 1e-9, qvel 1e-6, obs 1e-6, reward 1e-7 for every
+fp64 kernel (the default): qpos 1e-9, qvel 1e-6, obs 1e-6, reward 1e-7 and the warm start
+the step leaves (the last RK stage's solved qacc: the fast kernels' solve before h scales it)
+1e-7 relative to max(1, max|warm|), the forward tests' bound, for every
 env-step but at most ONE per test, and every env-step within qvel 2e-5.  The oracle
 restates MuJoCo's solver (PrimalSearch line search, improvement-or-gradient stop at 1e-8);
 the kernel keeps its own line search.  Where the two searches end an iteration at
@@ -13,7 +15,7 @@ teacher-forced env-steps, at qvel 1.0e-5 / qpos 5e-9 (profiles/r05_solver_parity
 Each test prints its worst errors and outlier count (DESIGN §4 keeps the measured ones).
 
 fp32 kernel: qpos 1e-5, qvel 1e-3, obs 1e-4, reward 1e-6 for
-at least 99.9% of env-steps; the rest must stay below qvel 1e-2.  Residual
+at least 99.9% of env-steps; the rest must stay below qvel 1e-2; the warm start finite.  Residual
 fp32 outliers are states where a wheel contact's drive-direction row (R scaled
 by (0.001/1.0)^2, ballbot.xml:90-92) makes the Newton Hessian ~1e10
 ill-conditioned for float arithmetic; DESIGN.md §fp32 documents them.
@@ -26,6 +28,7 @@ pytestmark = pytest.mark.gpu
 
 TOL = {"fp32": dict(q=1e-5, v=1e-3, obs=1e-4, r=1e-6, frac=0.999, vmax=1e-2),
        "fp64": dict(q=1e-9, v=1e-6, obs=1e-6, r=1e-7, max_bad=1, vmax=2e-5)}
+WARM_TOL = 1e-7  # fp64: the forward tests' qacc bound, relative to max(1, max|warm|)
 
 
 @pytest.fixture(scope="module")
@@ -56,7 +59,8 @@ def _teacher_forced(env, rec, tol):
     """Step every env from the oracle's pre-step state; compare post-step state/outputs."""
     bad = 0
     total = 0
-    worst = dict(q=0.0, v=0.0, obs=0.0, r=0.0)
+    worst = dict(q=0.0, v=0.0, obs=0.0, r=0.0, w=0.0)
+    fp64 = "max_bad" in tol
     for t in range(rec["qpos"].shape[0]):
         env.set_state(rec["qpos"][t], rec["qvel"][t], rec["warm"][t], rec["steps"][t])
         a = torch.tensor(rec["action"][t], dtype=torch.float32, device=env.device)
@@ -66,14 +70,19 @@ def _teacher_forced(env, rec, tol):
         ev = np.abs(v - rec["qvel1"][t]).max(axis=1)
         eo = np.abs(obs.cpu().numpy() - rec["obs"][t]).max(axis=1)
         er = np.abs(rew.cpu().numpy() - rec["reward"][t])
-        ok = (eq <= tol["q"]) & (ev <= tol["v"]) & (eo <= tol["obs"]) & (er <= tol["r"])
+        ok = state_ok = (eq <= tol["q"]) & (ev <= tol["v"]) & (eo <= tol["obs"]) & (er <= tol["r"])
+        # the warm start is the last RK stage's solved qacc: the solve itself, not yet multiplied by h
+        assert np.isfinite(w).all(), f"step {t}: warm start not finite"
+        ew = np.abs(w - rec["warm1"][t]).max(axis=1) / np.maximum(1.0, np.abs(rec["warm1"][t]).max(axis=1))
+        if fp64:
+            ok = state_ok & (ew <= WARM_TOL)
         bad += int((~ok).sum())
         total += len(ok)
-        for k, arr in (("q", eq), ("v", ev), ("obs", eo), ("r", er)):
+        for k, arr in (("q", eq), ("v", ev), ("obs", eo), ("r", er), ("w", ew)):
             worst[k] = max(worst[k], float(arr.max()))
         assert ev.max() <= tol["vmax"], f"step {t}: qvel error {ev.max():.3e} beyond outlier bound"
         gflags = info["done_flags"].cpu().numpy() & 3
-        mism = np.nonzero((gflags != (rec["flags"][t] & 3)) & ok)[0]
+        mism = np.nonzero((gflags != (rec["flags"][t] & 3)) & state_ok)[0]
         assert len(mism) == 0, f"step {t}: termination flags differ for envs {mism}"
     print(f"\nteacher-forced: {total} env-steps, {bad} outside tolerance, worst {worst}")
     if "max_bad" in tol:

@@ -27,6 +27,7 @@ TOL = dict(q=1e-9, v=1e-6, obs=1e-6, r=1e-7, max_bad=1, vmax=2e-5)
 # qvel 0.8 / qpos 5e-4 (round 6), where a wheel's drive-direction row makes the Newton Hessian
 # ~1e10-ill-conditioned for float; fp64, the default, holds qvel 2e-5 everywhere
 TOL32 = dict(q=1e-5, v=1e-3, obs=1e-4, r=1e-6, frac=0.999, vmax=None)
+WARM_TOL = 1e-7  # fp64, relative to max(1, max|warm|): test_gpu_parity.WARM_TOL
 
 
 @pytest.mark.parametrize("terrain,precision", [("perlin", "fp64"), ("hills", "fp64"), ("perlin", "fp32")])
@@ -51,14 +52,14 @@ def test_relief_pair_teacher_forced_vs_oracle(oracle, terrain, precision, monkey
     cfg = oracle.default_cfg()
     fields = {}
     bad = total = full_steps = big = 0
-    worst = dict(q=0.0, v=0.0, obs=0.0, r=0.0)
+    worst = dict(q=0.0, v=0.0, obs=0.0, r=0.0, w=0.0)
     s0 = env.stats()
     for t in range(48):
         q, v, w, sc = env.get_state()
         slots, _ = env.env_terrain()
         acts = torch.rand(1, n, 3, generator=g, device="cuda:0") * 2 - 1
         out = env.step_multi(acts)  # ONE pair launch of one step
-        q1, v1, _, _ = env.get_state()
+        q1, v1, w1, _ = env.get_state()
         pc = env.pair_counters()
         full_steps += pc["steps_full"]
         a_h = acts[0].cpu().numpy()
@@ -77,9 +78,14 @@ def test_relief_pair_teacher_forced_vs_oracle(oracle, terrain, precision, monkey
                 continue
             eq, ev = float(np.abs(q1[e] - qe).max()), float(np.abs(v1[e] - ve).max())
             eo, er = float(np.abs(obs[e] - o).max()), abs(float(rew[e]) - r)
+            # the warm start the step leaves (the last RK stage's solved qacc) against the oracle's: fp64 at
+            # test_gpu_parity's WARM_TOL inside the same outlier budget, fp32 finite
+            ew = float(np.abs(w1[e] - we).max() / max(1.0, np.abs(we).max()))
+            assert np.isfinite(ew), (t, e)
             total += 1
-            bad += not (eq <= tol["q"] and ev <= tol["v"] and eo <= tol["obs"] and er <= tol["r"])
-            for k, x in (("q", eq), ("v", ev), ("obs", eo), ("r", er)):
+            bad += not (eq <= tol["q"] and ev <= tol["v"] and eo <= tol["obs"] and er <= tol["r"]
+                        and (precision != "fp64" or ew <= WARM_TOL))
+            for k, x in (("q", eq), ("v", ev), ("obs", eo), ("r", er), ("w", ew)):
                 worst[k] = max(worst[k], x)
             big += ev > tol["v"] * 10
             assert tol["vmax"] is None or ev <= tol["vmax"], (t, e, ev)

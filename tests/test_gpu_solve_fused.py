@@ -31,10 +31,8 @@ def _quat_mul(a, b):
                      w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
 
 
-@pytest.fixture(scope="module")
-def states(oracle):
-    """(name, qpos, qvel, warm) of the three states; computed once, never modified."""
-    O = oracle
+def build_states(O):
+    """(name, qpos, qvel, warm) of the three states, read-only (tests/test_gpu_solve_regimes.py starts from them too)."""
     hf, cfg = O.flat_hfield(), O.default_cfg()
     q0, v0, w0 = O.reset_state(0.01)
     fall_q = q0.copy()
@@ -59,6 +57,12 @@ def states(oracle):
         for x in (a, b, c):
             x.setflags(write=False)
     return out
+
+
+@pytest.fixture(scope="module")
+def states(oracle):
+    """The three states; computed once, never modified."""
+    return build_states(oracle)
 
 
 @pytest.fixture(scope="module")

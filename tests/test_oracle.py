@@ -184,6 +184,53 @@ def test_static_ball_load_equals_weight(oracle):
     assert abs(ft - m[1:7].sum() * G) <= 0.01 * m[1:7].sum() * G, (ft, m[1:7].sum() * G)
 
 
+def test_contact_zone_agrees_with_force(oracle):
+    """con_zone is cone_eval's zone at the solution, so the contact's force says the same: zone 0 (top,
+    inactive) exactly zero, zone 1 (middle, sliding) on the friction cone f_n = |(f_1/mu_1, f_2/mu_2)|,
+    zone 2 (bottom, sticking) strictly inside it.  Friction (0.001, 1) for ball-wheel pairs (ballbot.xml:90-92),
+    (1, 1) for the terrain's.  States: a settled robot pressed 0 to 30 mm into hills terrain, lifted, spun."""
+    from ballbot_gym.terrain import generate_hills_terrain
+
+    hf = generate_hills_terrain(293, seed=7).astype(np.float32)
+    cfg = oracle.default_cfg()
+    q0, v0, w0 = oracle.reset_state(oracle.init_offset(hf))
+    for _ in range(200):
+        oracle.env_step(cfg, q0, v0, w0, np.zeros(1, np.int32), np.zeros(3, np.float32), hf)
+    rng = np.random.default_rng(4)
+    seen = {(wheel, z): 0 for wheel in (False, True) for z in (0, 1, 2)}
+    for i in range(720):
+        q, v = q0.copy(), v0 * (i % 2) + rng.normal(0, 1, 15) * (0.0, 1e-3, 0.3)[i % 3]
+        dz = -rng.uniform(0, 0.03) if i % 4 else 0.0
+        if i % 5 == 0:
+            v[2] += rng.uniform(0.2, 1.0)  # the base leaving the ball
+        if i % 5 == 1:
+            v[12:15] += [0, 0, rng.uniform(5, 30)]  # the ball spinning on the ground
+        if i >= 120:
+            # a wheel sticks only where it needs less than a thousandth of its load along its axis: the robot
+            # as it settled, the base and the ball turning about their z axes, no torque; about 1 state in 25
+            if seen[(True, 2)] >= 3:
+                break
+            dz, v = 0.0, np.zeros(15)
+            v[5], v[14] = rng.uniform(0, 3), rng.uniform(5, 30)
+        q[2] += dz
+        q[12] += dz
+        fo = oracle.forward(q, v, rng.uniform(-10, 10, 3) * (i % 3 == 0 and i < 120), w0, hf)
+        assert fo.ncon == 3 + fo.nground
+        for k in range(fo.ncon):
+            wheel = fo.con_body1[k] == 7
+            f = np.array(fo.con_force[3 * k:3 * k + 3])
+            ft = np.hypot(f[1] / (0.001 if wheel else 1.0), f[2])
+            z = fo.con_zone[k]
+            seen[(wheel, z)] += 1
+            if z == 0:
+                assert not f.any(), (i, k, f)
+            elif z == 1:
+                assert f[0] > 0 and abs(ft - f[0]) <= 1e-9 * f[0], (i, k, f)
+            else:
+                assert z == 2 and f[0] > 0 and ft < f[0], (i, k, f)
+    assert all(n >= 3 for n in seen.values()), seen
+
+
 def test_patched_contact_frame(oracle):
     """tools/mujoco_fix.patch: the first tangent of each ball-wheel contact is
     the capsule axis orthogonalised against the normal; the frame is orthonormal
