@@ -24,6 +24,7 @@
  *   bb_ppo_mlp_act   SB3 collect_rollouts policy step (same policy)
  *   bb_rollout_track SB3 collect_rollouts / Monitor episode bookkeeping
  *   bb_rollout       a whole SB3 collect_rollouts (policy + step + bookkeeping) in one launch
+ *   bb_reward_terms  reward_term_1_hist / reward_term_2_hist of _save_logs  ballbot_env.py:929-937, 673-699
  *   bb_depth_encoder frozen rgbd encoder of the camera policy, fused
  *   bb_gae           SB3 RolloutBuffer.compute_returns_and_advantage (PPO)
  *   bb_forward       mujoco.mj_forward (diagnostic)             ballbot_env.py:525,620
@@ -56,7 +57,7 @@
 extern "C" {
 #endif
 
-#define BB_ABI_VERSION 19
+#define BB_ABI_VERSION 20
 #define BB_NQ 17
 #define BB_NV 15
 #define BB_OBS 15
@@ -276,8 +277,33 @@ typedef struct bb_rollout_args {
   uint8_t* buf_starts;      /* [T][n] episode_starts of each step */
   double* ep_r_out;         /* [T][n] finished episodes' returns, NaN elsewhere */
   int64_t* ep_l_out;        /* [T][n] their lengths, 0 elsewhere */
+  /* optional (ABI 20; both NULL: not written, the launch is what it was; else both set): what the
+   * auto-reset inside the launch destroys, for bb_reward_terms -- the observation after each step
+   * and before any auto-reset (bb_step_multi's terminal_obs rows), and the step's BB_DONE_* bits */
+  float* buf_terminal_obs;  /* [T][n][15] */
+  uint8_t* buf_flags;       /* [T][n] */
 } bb_rollout_args;
 int bb_rollout(bb_handle* h, const bb_rollout_args* args, void* stream);
+/* The reward terms of k_steps env.steps, as the reference logs them per episode
+ * (reward_term_1_hist / reward_term_2_hist, ballbot_env.py:929-937, written by _save_logs,
+ * :673-699): from the post-step observation rows obs_dev float[k][n][15] (bb_step's or
+ * bb_step_multi's terminal_obs, or bb_rollout's buf_terminal_obs) and the handle's reward
+ * settings,
+ *   term_1 = (vel_x * target_x + vel_y * target_y) * reward_scale      vel = obs[12:15]
+ *   term_2 = action_reg_coef * (|a| * |a|)                             a   = obs[0:3]
+ * in the step kernels' own float32 operation order, so they are the very floats the step
+ * added: reward == fl32(fl32(term_1 + term_2) + survival_bonus), without the bonus on a
+ * failure step.  book_dev int64[2 n + 2] (caller-owned, zeroed before the first call) keeps the
+ * bookkeeping on the device: book[2n] counts the steps recorded so far; row j of this call is
+ * global step g = book[2n] + j and its terms go to terms_dev[g][n][2] (float32; a history of
+ * terms_rows steps that consecutive calls walk through -- rows at or past terms_rows are
+ * dropped, which the caller sees as book[2n] > terms_rows); for each env e whose flags_dev
+ * uint8[k][n] row has BB_DONE_TERMINATED, book[e] = g + 1 of its last such row and book[n + e]
+ * counts them; the call ends with book[2n] advanced by k_steps (book[2n + 1] is the kernel's
+ * scratch).  BB_REWARD_DIRECTIONAL handles only.  One launch on stream, no allocation, no
+ * sync, no host read: graph-capturable. */
+int bb_reward_terms(bb_handle* h, const float* obs_dev, const uint8_t* flags_dev, int k_steps, float* terms_dev,
+                    int64_t terms_rows, int64_t* book_dev, void* stream);
 /* One rollout step's episode bookkeeping (SB3 collect_rollouts + Monitor,
  * model.learn at ballbot_rl/training/train.py:284): done = (flags_dev[i] &
  * done_mask) != 0; rewards_out_dev[i] = reward_dev[i]; the float64 episode

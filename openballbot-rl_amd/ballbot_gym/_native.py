@@ -89,7 +89,7 @@ class RolloutArgs(C.Structure):
         ("n_steps", C.c_int32),
     ] + [(name, C.c_void_p) for name in ("obs", "last_starts", "ep_ret", "ep_len", "buf_obs", "buf_actions",
                                          "buf_values", "buf_log_prob", "buf_rewards", "buf_starts", "ep_r_out",
-                                         "ep_l_out")]
+                                         "ep_l_out", "buf_terminal_obs", "buf_flags")]
 
 
 ENCODER_FIELDS = ("conv1_w", "conv1_b", "bn1_w", "bn1_b", "bn1_mean", "bn1_var", "bn1_count",
@@ -110,15 +110,16 @@ EXPORTS = [
     "bb_ppo_mlp_act", "bb_rollout_track", "bb_depth_encoder_workspace_bytes", "bb_depth_encoder",
     "bb_set_terrain_stream", "bb_get_env_terrain", "bb_kernel_times", "bb_step_multi", "bb_rollout",
     "bb_set_terrain_rng", "bb_get_terrain_rng", "bb_pair_counters", "bb_pair_env_times", "bb_check",
+    "bb_reward_terms",
 ]
 
-ABI_VERSION = 19  # include/ballbot_mi355x.h BB_ABI_VERSION
+ABI_VERSION = 20  # include/ballbot_mi355x.h BB_ABI_VERSION
 
 _lib = None
 
 
 HIP_SOURCES = ("bb_kernels.hip", "bb_pair.hip", "bb_terrain.hip", "bb_rollout.hip", "bb_render.hip", "bb_ppo.hip",
-               "bb_mlp.hip", "bb_encoder.hip")
+               "bb_mlp.hip", "bb_encoder.hip", "bb_episode_log.hip")
 # per-source flags: the relief pair's unit without MachineLICM (bb_kernels.hip: bb_pair_launch_tu)
 SOURCE_FLAGS = {"bb_pair.hip": ["-mllvm", "-disable-machine-licm"]}
 
@@ -196,6 +197,7 @@ def _load(path: Path):
     L.bb_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]
     L.bb_step_multi.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
     L.bb_rollout.argtypes = [vp, C.POINTER(RolloutArgs), vp]
+    L.bb_reward_terms.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int64, vp, vp]
     L.bb_get_state.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_int32)]
     L.bb_set_state.argtypes = [vp, dp, dp, dp, C.POINTER(C.c_int32)]
     L.bb_forward.argtypes = [vp, dp, dp, C.POINTER(C.c_int32)]

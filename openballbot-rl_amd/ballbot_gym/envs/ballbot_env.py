@@ -22,8 +22,19 @@ host runs that generator and generates the drawn terrain into a small ring of
 bank slots (the GPU perlin generator, or the registered plugin), as the
 reference regenerates the heightfield at every reset (:501-513).
 
-Not provided: the MuJoCo viewer (GUI), RGB video rendering (`render()`) and
-the per-episode log files (_save_logs) -- outside the hot path.
+Per-episode logs as the reference writes them (_save_logs, :673-699, through
+utils/logging.py): with a `log_options` switch on (`reward_terms`, `cams`, or
+`terrain_seeds`; the `logging` section of env_config overrides them, :214-218)
+a non-eval env creates `<log_options["dir"] or /tmp>/log_<12 chars>` at its
+first reset -- the name is the first 12 characters of the permutation drawn
+there (:655-669) -- and every terminated step writes term_1.npy / term_2.npy
+(the recorder kernel's terms of every step since construction: the reference
+never clears them, :370-372), appends the episode's terrain seed to
+terrain_seed_history (perlin) and, with `cams`, dumps the depth frames rendered
+during the episode's steps.  With every switch off no directory is created.
+
+Not provided: the MuJoCo viewer (GUI) and RGB video rendering (`render()`) --
+outside the hot path.
 """
 from __future__ import annotations
 
@@ -70,7 +81,10 @@ class BBotSimulation:
             "max_ep_steps", max_ep_steps if max_ep_steps is not None else 4000))
         self.disable_cameras = bool(disable_cameras)
         self.xml_path = xml_path
-        self.log_options = log_options or {"cams": False, "reward_terms": False}
+        # the `logging` section of env_config overrides log_options (ballbot_env.py:214-218)
+        self.log_options = {"cams": False, "reward_terms": False, **(log_options or {}),
+                            **(env_config.pop("logging", None) or {})}
+        self.depth_only = True
         self.render_mode = render_mode if render_mode is not None else "rgb_array"
         self.viewer_title = viewer_title
         self.passive_viewer = None
@@ -95,6 +109,24 @@ class BBotSimulation:
                                   max_ep_steps=max_ep_steps, precision=precision, auto_reset=False,
                                   disable_cameras=self.disable_cameras, terrain_slots=self._ring,
                                   reward_compat=reward_compat)
+        # per-episode logs (ballbot_env.py:280-288, 362-372): host histories, as the reference keeps them
+        self.rgbd_hist_0, self.rgbd_hist_1 = [], []
+        self.reward_term_1_hist, self.reward_term_2_hist = [], []  # never cleared (the reference's quirk)
+        self._logs_on = any(bool(self.log_options.get(k)) for k in ("cams", "reward_terms", "terrain_seeds"))
+        self._log_cams = bool(self.log_options.get("cams")) and not self.disable_cameras
+        self._log_terms = bool(self.log_options.get("reward_terms"))
+        if self._log_terms:
+            import torch
+
+            from .. import _native as N
+
+            if self._env._params.reward_kind != N.REWARD_DIRECTIONAL:
+                raise ValueError("log_options['reward_terms'] needs the built-in directional reward, got "
+                                 f"{type(self._env.reward_obj).__name__}: the reference env logs the terms of that "
+                                 "reward only (ballbot_env.py:929-937)")
+            # the recorder's one-step outputs (bb_reward_terms): terms [1][1][2], bookkeeping [2 n + 2]
+            self._terms = torch.zeros(1, 1, 2, dtype=torch.float32, device=self._env.device)
+            self._book = torch.zeros(4, dtype=torch.int64, device=self._env.device)
 
     @property
     def opt_timestep(self) -> float:
@@ -139,13 +171,23 @@ class BBotSimulation:
         r_seed = int(gen.integers(0, TERRAIN_SEED_HIGH)) if cfg_seed is None else int(cfg_seed)
         self.last_r_seed = r_seed
         if not self.eval_env and not self._log_drawn:  # the /tmp/log_<12 chars> name (ballbot_env.py:655-661)
-            gen.permutation(list(string.ascii_letters + string.digits))
+            perm = gen.permutation(list(string.ascii_letters + string.digits))
             self._log_drawn = True
+            if self._logs_on:  # created only when something will be written into it
+                import os
+                import shutil
+
+                self.log_dir = os.path.join(str(self.log_options.get("dir") or "/tmp"), "log_" + "".join(perm[:12]))
+                if os.path.exists(self.log_dir):  # "already exists. Overwriting!" (ballbot_env.py:664-666)
+                    shutil.rmtree(self.log_dir)
+                os.makedirs(self.log_dir)
         self._env.assign_terrain(np.array([self._slot(r_seed)], np.int32))
         self._env.reset()
         self.num_episodes += 1
         self.step_counter = 0
         obs = self._obs()
+        # after the reset's own render, which is therefore not logged (ballbot_env.py:634-641)
+        self.rgbd_hist_0, self.rgbd_hist_1 = [], []
         return obs, self._info(np.zeros(2, np.float32), False)
 
     def step(self, action):
@@ -156,8 +198,37 @@ class BBotSimulation:
         obs, rew, term, trunc, info = self._env.step(torch.from_numpy(a).to(self._env.device))
         self.step_counter += 1
         fl = int(info["done_flags"][0].item())
-        return (self._obs(), float(rew[0].item()), bool(fl & 1), False,
+        o = self._obs()
+        if self._log_cams and float(o["relative_image_timestamp"][0]) == 0.0:  # a fresh render (ballbot_env.py:750-758)
+            self.rgbd_hist_0.append(o["rgbd_0"].copy())
+            self.rgbd_hist_1.append(o["rgbd_1"].copy())
+        if self._log_terms:
+            t1, t2 = self._reward_terms()
+            self.reward_term_1_hist.append(t1)
+            self.reward_term_2_hist.append(t2)
+        if (fl & 1) and self.log_dir is not None:  # _save_logs (ballbot_env.py:1027-1034)
+            from ..utils.logging import save_episode_logs
+
+            save_episode_logs(self.log_dir, self.rgbd_hist_0, self.rgbd_hist_1, self.reward_term_1_hist,
+                              self.reward_term_2_hist, self.last_r_seed if self.terrain_type == "perlin" else None,
+                              self.terrain_type, self.depth_only, self.log_options, self.num_episodes, self.eval_env)
+        return (o, float(rew[0].item()), bool(fl & 1), False,
                 self._info(info["pos2d"][0].cpu().numpy().astype(np.float32), bool(fl & 2)))
+
+    def _reward_terms(self):
+        """This step's (term_1, term_2) as float32, from the recorder kernel over the step's
+        terminal observation (bb_reward_terms: the floats the step kernel added)."""
+        import ctypes as C
+
+        from .. import _native as N
+
+        env = self._env
+        self._book.zero_()  # one-row history: the recorder's step counter restarts at row 0
+        N.check(N.lib().bb_reward_terms(env._h, C.c_void_p(env.terminal_obs.data_ptr()),
+                                        C.c_void_p(env.done.data_ptr()), 1, C.c_void_p(self._terms.data_ptr()), 1,
+                                        C.c_void_p(self._book.data_ptr()), env._stream()), "bb_reward_terms")
+        t = self._terms.cpu().numpy().reshape(2)
+        return np.float32(t[0]), np.float32(t[1])
 
     def close(self):
         if self._env is not None:

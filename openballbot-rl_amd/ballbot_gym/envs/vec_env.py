@@ -43,6 +43,16 @@ class BallbotVecEnv:
     whose terrains a host-generated bank holds (perlin default: the whole
     10^4-seed space, generated on the GPU).  `terrain_draws`: an explicit list
     of terrain seeds that every env walks instead (a replayed draw log).
+
+    `log_options` (with env_config's `logging` section on top, ballbot_env.py:214-218)
+    turns on the reference's per-episode log files (_save_logs, :673-699): keys
+    `reward_terms` (term_1.npy / term_2.npy), `terrain_seeds` (terrain_seed_history),
+    `envs` (local indices of the envs that log; None: all), `dir` (env i logs under
+    dir/env_{first_env + i:05d}/; default: a fresh temporary directory) and `cams`
+    (refused: frame dumps are BBotSimulation's).  Both switches need the built-in
+    directional reward.  The files are current after flush_logs() -- see the
+    "per-episode logs" section below.  With every switch off (the default) no launch,
+    buffer or file is added.
     """
 
     metadata = {"render_modes": []}
@@ -68,9 +78,12 @@ class BallbotVecEnv:
         reward_compat: str = "reference",
         opt_timestep: Optional[float] = None,
         opt_disableflags: int = 0,
+        log_options: Optional[Dict[str, Any]] = None,
+        first_env: int = 0,
     ):
         from .config import params_from_configs
 
+        self._log_on = False  # the per-episode logs (log_options), set up after the first reset
         if not torch.cuda.is_available():
             raise RuntimeError("BallbotVecEnv needs a ROCm GPU (torch.cuda.is_available() is False)")
         self.device = torch.device(device)
@@ -97,6 +110,8 @@ class BallbotVecEnv:
         # reward_compat="reference": a DistanceReward raises at the first step, as
         # in the reference env (its obs lacks pos2d); "fused": the kernel computes it
         self._reward_error = reward_error(self.reward_obj, reward_compat)
+        self.first_env = int(first_env)  # global id of env 0 (a rank's block, distributed.env_shard)
+        self.log_options = self._log_config(log_options, env_config, p)
         # mjModel.opt overrides (physics invariant tests): timestep and MuJoCo's
         # mjDSBL_PASSIVE / mjDSBL_GRAVITY bits (_native.DSBL_*); the reference never sets them
         p.opt_timestep = float(opt_timestep or 0.0)
@@ -134,6 +149,7 @@ class BallbotVecEnv:
         self.observation_space = spaces.observation_space({"h": self.cam_h, "w": self.cam_w}, 1, not self.cameras)
         self._pending_actions: Optional[torch.Tensor] = None
         self.reset()  # the first reset: draw 0 of every env's generator
+        self._log_alloc()
 
     # ------------------------------------------------------------ terrain bank
     def _plan(self, stream_seeds=None, terrain_draws=None):
@@ -234,6 +250,9 @@ class BallbotVecEnv:
         """Reset every env (mask None) or the masked ones -> (obs, {}).  A full
         reset first applies the seeds of seed(), as SB3's VecEnv.reset passes
         seed + i to env i's reset (then forgets them)."""
+        seed_log = self._log_on and self._log_seeds and not torch.cuda.is_current_stream_capturing()
+        if seed_log:  # the episodes finished so far belong to the draws (and generators) before this reset
+            self.flush_logs()
         if mask is None and self._pending_seeds is not None:
             pending, self._pending_seeds = self._pending_seeds, None
             self._reseed(pending)
@@ -241,6 +260,8 @@ class BallbotVecEnv:
         N.check(N.lib().bb_reset(self._h, _ptr(m), _ptr(self.obs), self._stream()), "bb_reset")
         if self.cameras:
             self._render(force=m is None)
+        if seed_log:
+            self._log_rebase()
         return self.obs, {}
 
     def _render(self, force: bool) -> None:
@@ -265,6 +286,7 @@ class BallbotVecEnv:
                 "bb_step")
         if self.cameras:  # envs whose counter hit the frame interval (incl. auto-resets) re-render
             self._render(force=False)
+        self._record(self.terminal_obs, self.done, 1)
         if self._reward_error:  # after mj_step, as the reference's reward call (ballbot_env.py:912, 929)
             raise ValueError(self._reward_error)
         terminated = (self.done & N.DONE_TERMINATED) != 0
@@ -292,6 +314,7 @@ class BallbotVecEnv:
                 "bb_step")
         if self.cameras:
             self._render(force=False)
+        self._record(self.terminal_obs, self.done, 1)
         return self.obs, self.reward, self.done
 
     def capture_step(self, actions: torch.Tensor) -> "torch.cuda.CUDAGraph":
@@ -314,8 +337,12 @@ class BallbotVecEnv:
 
     def note_graph_capture(self) -> None:
         """Record that a HIP graph holding this env's handle exists (it lives as long as the env):
-        a re-seed that would need a new handle then raises instead of leaving the graph stale."""
+        a re-seed that would need a new handle then raises instead of leaving the graph stale.
+        A graph captured over an env that logs holds the log history's address: the history can no
+        longer move, so it must have been sized before (reserve_log_rows)."""
         self._graphs += 1
+        if self._log_on:
+            self._log_pinned = True
 
     def _step_launch(self, actions: torch.Tensor) -> None:
         N.check(N.lib().bb_step(self._h, _ptr(actions), _ptr(self.obs), _ptr(self.reward), _ptr(self.done),
@@ -323,6 +350,7 @@ class BallbotVecEnv:
                 "bb_step")
         if self.cameras:
             self._render(force=False)
+        self._record(self.terminal_obs, self.done, 1)
 
     def step_multi(self, actions: torch.Tensor, out: Optional[dict] = None) -> dict:
         """K env.steps of all envs in ONE launch for actions known in advance
@@ -351,16 +379,20 @@ class BallbotVecEnv:
         N.check(N.lib().bb_step_multi(self._h, _ptr(actions), k, _ptr(out["obs"]), _ptr(out["reward"]),
                                       _ptr(out["done"]), _ptr(out["terminal_obs"]), _ptr(out["pos2d"]),
                                       int(self.auto_reset), self._stream()), "bb_step_multi")
+        self._record(out["terminal_obs"], out["done"], k)
         return out
 
     def step_multi_raw(self, actions: torch.Tensor, obs: torch.Tensor, reward: torch.Tensor,
                        done: torch.Tensor, terminal_obs: Optional[torch.Tensor] = None,
                        pos2d: Optional[torch.Tensor] = None) -> None:
         """Launch-only bb_step_multi (benchmarking): caller-owned [K, N, ...] outputs
-        (terminal obs / pos2d optional)."""
+        (terminal obs / pos2d optional; an env that logs needs the terminal obs)."""
+        if self._log_on and terminal_obs is None:
+            raise ValueError("this env records per-episode logs (log_options): step_multi_raw needs terminal_obs")
         N.check(N.lib().bb_step_multi(self._h, _ptr(actions), int(actions.shape[0]), _ptr(obs), _ptr(reward),
                                       _ptr(done), _ptr(terminal_obs), _ptr(pos2d), int(self.auto_reset),
                                       self._stream()), "bb_step_multi")
+        self._record(terminal_obs, done, int(actions.shape[0]))
 
     def check(self) -> None:
         """Wait for the env's stream and raise if a bb_step_multi relief-pair launch ended on its
@@ -377,15 +409,22 @@ class BallbotVecEnv:
             raise RuntimeError("bb_rollout needs a built-in reward (a host plugin runs per step())")
         if self._reward_error:
             raise ValueError(self._reward_error)
+        if self._log_on and self._log_recording and not (args.buf_terminal_obs and args.buf_flags):
+            raise RuntimeError("this env records per-episode logs (log_options): the rollout needs "
+                               "buf_terminal_obs and buf_flags ([T][n][15] float32, [T][n] uint8)")
         N.check(N.lib().bb_rollout(self._h, C.byref(args), self._stream()), "bb_rollout")
+        if args.buf_terminal_obs and args.buf_flags:
+            self._record(C.c_void_p(args.buf_terminal_obs), C.c_void_p(args.buf_flags), int(args.n_steps))
 
     def step_async_raw(self, actions: torch.Tensor, full_outputs: bool = False) -> None:
         """Launch-only step (graph capture / benchmarking): no derived tensors;
-        full_outputs: also the terminal obs and pos2d buffers."""
+        full_outputs: also the terminal obs and pos2d buffers (an env that logs always
+        keeps the terminal obs: its recorder reads them)."""
         N.check(N.lib().bb_step(self._h, _ptr(actions), _ptr(self.obs), _ptr(self.reward), _ptr(self.done),
-                                _ptr(self.terminal_obs) if full_outputs else None,
+                                _ptr(self.terminal_obs) if full_outputs or self._log_on else None,
                                 _ptr(self.pos2d) if full_outputs else None, int(self.auto_reset), self._stream()),
                 "bb_step")
+        self._record(self.terminal_obs, self.done, 1)
 
     def _plugin_reward(self, failure: torch.Tensor) -> torch.Tensor:
         """Reward of a custom plugin, in the reference's float32 order
@@ -412,6 +451,205 @@ class BallbotVecEnv:
             v = torch.from_numpy(out).to(self.device)
         r = v * f32(self._params.reward_scale) + self.reward
         return torch.where(failure, r, r + f32(self._params.survival_bonus))
+
+    # ------------------------------------------------------- per-episode logs
+    # The reference env writes, when an episode ends (_save_logs, ballbot_env.py:673-699):
+    # term_1.npy / term_2.npy (the reward's two terms per step) and one line of
+    # terrain_seed_history.  Here a recorder kernel (bb_reward_terms) follows every step
+    # launch on the same stream: it appends the steps' [K][n][2] terms to a device-resident
+    # history and keeps, per env, the step of its last terminal row and its count of
+    # finished episodes.  Nothing is copied to the host per step; flush_logs() writes the
+    # files.  The one deliberate difference from the reference: the files are current after
+    # flush_logs() (close() flushes; the trainer flushes at every update boundary), not
+    # after every step.
+    def _log_config(self, log_options, env_config, p) -> Dict[str, Any]:
+        """log_options (keys reward_terms, cams, terrain_seeds, envs, dir) with env_config's
+        `logging` section on top, as the reference overrides them (ballbot_env.py:214-218)."""
+        opts: Dict[str, Any] = {"reward_terms": False, "cams": False, "terrain_seeds": False, "envs": None,
+                                "dir": None}
+        opts.update(log_options or {})
+        opts.update((env_config or {}).get("logging", {}) or {})
+        if opts["cams"]:
+            raise ValueError("log_options['cams']: per-episode frame dumps are a single-env feature "
+                             "(BBotSimulation(log_options={'cams': True})); the batched env writes no frames")
+        if (opts["reward_terms"] or opts["terrain_seeds"]) and p.reward_kind != N.REWARD_DIRECTIONAL:
+            what = "reward_terms" if opts["reward_terms"] else "terrain_seeds"
+            raise ValueError(f"log_options[{what!r}] needs the built-in directional reward, got "
+                             f"{type(self.reward_obj).__name__}: the reference env logs the terms of that reward "
+                             "only (ballbot_env.py:929-937), and the recorder that also counts the finished "
+                             "episodes (bb_reward_terms) computes them")
+        if opts["envs"] is not None:
+            envs = sorted({int(i) for i in opts["envs"]})
+            if envs and not (0 <= envs[0] and envs[-1] < self.num_envs):
+                raise ValueError(f"log_options['envs'] must be indices in [0, {self.num_envs}), got {opts['envs']}")
+            opts["envs"] = envs
+        return opts
+
+    LOG_ROWS0 = 256  # first allocation of the term history, in steps (doubled as it fills)
+
+    def _log_alloc(self) -> None:
+        o = self.log_options
+        self._log_terms, self._log_seeds = bool(o["reward_terms"]), bool(o["terrain_seeds"])
+        self._log_recording = True
+        self._log_pinned = False  # a captured graph holds the history's address
+        self.log_dir = None
+        if not (self._log_terms or self._log_seeds):
+            return
+        import os
+        import tempfile
+
+        n, dev = self.num_envs, self.device
+        self.log_dir = str(o["dir"]) if o["dir"] else tempfile.mkdtemp(prefix="ballbot_env_logs_")
+        os.makedirs(self.log_dir, exist_ok=True)
+        self._log_envs = list(range(n)) if o["envs"] is None else list(o["envs"])
+        self._log_idx = None if o["envs"] is None else torch.tensor(self._log_envs, dtype=torch.int64, device=dev)
+        # recorder state (bb_reward_terms): [0:n] last terminal step + 1, [n:2n] finished episodes,
+        # [2n] steps recorded, [2n+1] kernel scratch
+        self._log_book = torch.zeros(2 * n + 2, dtype=torch.int64, device=dev)
+        self._log_hist = torch.zeros(self.LOG_ROWS0, n, 2, dtype=torch.float32, device=dev)
+        self._log_rows = 0  # host mirror of book[2n]
+        self._log_flushed = 0  # ... at the last flush_logs()
+        self._log_written = np.zeros(n, np.int64)  # finished episodes already in the files
+        self._log_draw_base = np.zeros(n, np.int64)  # terrain draw index of an env's episode k = base + k
+        self._log_draws: Dict[int, np.ndarray] = {}
+        self._log_on = True
+
+    def reserve_log_rows(self, rows: int, recapture: bool = False) -> None:
+        """Room for `rows` more recorded steps in the device-resident term history.  Growing
+        moves the history (a stream-ordered copy).  A HIP graph captured over this env holds its
+        address, so reserve before capturing; recapture=True grows anyway -- the caller then
+        drops the graphs it captured over this env and captures them again."""
+        if not self._log_on:
+            return
+        need, cap = self._log_rows + int(rows), int(self._log_hist.shape[0])
+        if need <= cap:
+            return
+        if torch.cuda.is_current_stream_capturing() or (self._log_pinned and not recapture):
+            raise RuntimeError(f"the log history holds {cap} steps and {need} are needed, but a captured HIP graph "
+                               "holds its address: call reserve_log_rows() before capturing")
+        new = torch.zeros(max(need, 2 * cap), self.num_envs, 2, dtype=torch.float32, device=self.device)
+        new[:cap].copy_(self._log_hist)
+        self._log_hist = new
+        self._log_pinned = False
+
+    def log_rows_free(self) -> int:
+        """Steps the term history still has room for before it must grow (reserve_log_rows)."""
+        return int(self._log_hist.shape[0]) - self._log_rows if self._log_on else 1 << 62
+
+    def set_log_recording(self, on: bool) -> None:
+        """Pause / resume the recorder (steps taken while paused never enter the history)."""
+        self._log_recording = bool(on)
+
+    def note_log_rows(self, rows: int) -> None:
+        """Tell the env that a replayed graph (capture_step, the trainer's rollout graph)
+        recorded `rows` more steps: the recorder's launches inside it advanced the device
+        counter, and flush_logs() sizes its copy from the host's count."""
+        if self._log_on:
+            self._log_rows += int(rows)
+
+    def _record(self, terminal_obs, flags, k: int) -> None:
+        """Launch the recorder over k steps' rows (terminal obs [k][n][15], done bytes [k][n];
+        tensors or raw device pointers) on the current stream."""
+        if not (self._log_on and self._log_recording):
+            return
+        self.reserve_log_rows(k)
+        tp = terminal_obs if isinstance(terminal_obs, C.c_void_p) else _ptr(terminal_obs)
+        fp = flags if isinstance(flags, C.c_void_p) else _ptr(flags)
+        N.check(N.lib().bb_reward_terms(self._h, tp, fp, int(k), _ptr(self._log_hist), int(self._log_hist.shape[0]),
+                                        _ptr(self._log_book), self._stream()), "bb_reward_terms")
+        if not torch.cuda.is_current_stream_capturing():  # a captured launch runs at replay (note_log_rows)
+            self._log_rows += int(k)
+
+    def log_state(self):
+        """(terms [rows][N][2] float32 device view of the history, last terminal step + 1 per env
+        int64[N], finished episodes per env int64[N]) -- waits for the stream."""
+        if not self._log_on:
+            raise RuntimeError("this env records no per-episode logs (log_options)")
+        book = self._log_book.cpu().numpy()
+        n = self.num_envs
+        rows = min(int(book[2 * n]), int(self._log_hist.shape[0]))
+        return self._log_hist[:rows], book[:n].copy(), book[n:2 * n].copy()
+
+    def _log_seed(self, e: int, k: int):
+        """Terrain seed of env e's draw k (its k-th reset since its generator was installed)."""
+        plan = self.terrain_plan
+        if plan.stream_seeds is not None:
+            from .config import stream_draws
+
+            s = int(plan.stream_seeds[e])
+            d = self._log_draws.get(s)
+            if d is None or len(d) <= k:
+                d = self._log_draws[s] = stream_draws(s, max(2 * (k + 1), 16))
+            return int(d[k])
+        if plan.streams is not None:  # the terrain_draws table (wraps around, as on the device)
+            row = 0 if plan.env_stream is None else int(plan.env_stream[e])
+            return int(plan.seeds[int(plan.streams[row][k % plan.streams.shape[1]])])
+        return int(plan.seeds[0]) if plan.seeds and int(plan.seeds[0]) >= 0 else None  # a fixed config seed
+
+    def flush_logs(self) -> None:
+        """Bring the log files up to date: one wait for the stream, then, for every logged env
+        whose count of finished episodes advanced since the last flush,
+        <dir>/env_{global id:05d}/term_1.npy and term_2.npy -- every step since construction up
+        to the env's last terminal step (the reference never clears its term histories,
+        ballbot_env.py:370-372) -- and one terrain_seed_history line per newly finished episode
+        (perlin terrains).  Files are written by utils.logging.save_episode_logs."""
+        if not self._log_on or self._h is None:
+            return
+        import os
+
+        from ..utils.logging import save_episode_logs
+
+        if self._log_rows == self._log_flushed and not self._log_pinned:
+            return  # nothing was recorded since the last flush (replayed graphs may not have reported)
+        n, cap = self.num_envs, int(self._log_hist.shape[0])
+        stream = torch.cuda.current_stream(self.device)
+        book_h = torch.empty(2 * n + 2, dtype=torch.int64, pin_memory=True)
+        book_h.copy_(self._log_book, non_blocking=True)
+
+        def fetch(rows: int):
+            src = self._log_hist[:rows] if self._log_idx is None else self._log_hist[:rows].index_select(
+                1, self._log_idx)
+            out = torch.empty(src.shape, dtype=torch.float32, pin_memory=True)
+            out.copy_(src, non_blocking=True)
+            return out
+
+        rows = min(self._log_rows, cap)
+        hist_h = fetch(rows) if self._log_terms and rows else None
+        stream.synchronize()
+        book = book_h.numpy()
+        recorded = int(book[2 * n])
+        if recorded > cap:
+            import warnings
+
+            warnings.warn(f"the log history holds {cap} steps but {recorded} were recorded (graph replays past "
+                          "reserve_log_rows): the steps past it are missing from term_*.npy")
+        if self._log_terms and min(recorded, cap) > rows:  # a graph replay nobody reported (note_log_rows)
+            rows = min(recorded, cap)
+            hist_h = fetch(rows)
+            stream.synchronize()
+        self._log_rows = self._log_flushed = max(self._log_rows, recorded)
+        terms = None if hist_h is None else hist_h.numpy()
+        ttype = self.terrain_config.get("type", "flat")
+        for col, e in enumerate(self._log_envs):
+            done_eps = int(book[n + e])
+            first = int(self._log_written[e])
+            if done_eps <= first:
+                continue
+            env_dir = os.path.join(self.log_dir, f"env_{self.first_env + e:05d}")
+            os.makedirs(env_dir, exist_ok=True)
+            last = min(int(book[e]), rows)
+            for ep in range(first, done_eps):
+                final = ep == done_eps - 1  # the .npy files are overwritten: only the last write stays
+                seed = self._log_seed(e, ep + int(self._log_draw_base[e])) if self._log_seeds else None
+                save_episode_logs(env_dir, [], [], terms[:last, col, 0] if (final and terms is not None) else [],
+                                  terms[:last, col, 1] if (final and terms is not None) else [], seed, ttype, True,
+                                  {"cams": False, "reward_terms": self._log_terms and final}, ep, False)
+            self._log_written[e] = done_eps
+
+    def _log_rebase(self) -> None:
+        """After a reset() by the caller: the envs' draw counters moved without an episode ending."""
+        _, draws = self.env_terrain()
+        self._log_draw_base = draws.astype(np.int64) - 1 - self._log_written
 
     # ------------------------------------------------- SB3 VecEnv interface
     def step_async(self, actions) -> None:
@@ -611,6 +849,8 @@ class BallbotVecEnv:
 
     def close(self):
         if getattr(self, "_h", None):
+            if getattr(self, "_log_on", False):
+                self.flush_logs()
             N.lib().bb_destroy(self._h)
             self._h = None
 

@@ -552,6 +552,10 @@ class _RolloutGraph:
         self.flat = ppo.optimizer.flat
         self.offs = (C.c_int32 * 21)(*slots)
         lib = N.lib()
+        # an env that writes per-episode logs launches its recorder inside step_flags, so the graph
+        # holds the log history's address: size it for the run before capturing
+        if getattr(env, "_log_on", False):
+            env.reserve_log_rows(max(T, getattr(ppo, "_log_rows_ahead", 0)), recapture=True)
         obs = env.obs  # step_flags returns the env's own observation buffer: read in place
         flat, nflat = C.c_void_p(self.flat.data_ptr()), int(self.flat.numel())
         torch.cuda.synchronize(dev)
@@ -583,6 +587,8 @@ class _RolloutGraph:
         _dbg("rollout graph: before replay")
         self.graph.replay()
         _dbg("rollout graph: replayed")
+        if getattr(self.env, "_log_on", False):
+            self.env.note_log_rows(ppo.n_steps)  # the recorder launches inside the graph
         ppo._last_obs = self.env.obs
         return self.ep_r, self.ep_l
 
@@ -794,6 +800,13 @@ class BatchedPPO:
         a.buf_obs, a.buf_actions, a.buf_values = b.obs.data_ptr(), b.actions.data_ptr(), b.values.data_ptr()
         a.buf_log_prob, a.buf_rewards, a.buf_starts = b.log_probs.data_ptr(), b.rewards.data_ptr(), b.starts.data_ptr()
         a.ep_r_out, a.ep_l_out = ep_r.data_ptr(), ep_l.data_ptr()
+        if getattr(env, "_log_on", False):
+            # an env that writes per-episode logs: keep what the auto-reset inside the launch destroys
+            # (each step's terminal observation and done bits); run_rollout's recorder reads them
+            if getattr(self, "_log_tobs", None) is None or self._log_tobs.shape[:2] != (T, n):
+                self._log_tobs = torch.zeros(T, n, 15, device=dev)
+                self._log_flags = torch.zeros(T, n, dtype=torch.uint8, device=dev)
+            a.buf_terminal_obs, a.buf_flags = self._log_tobs.data_ptr(), self._log_flags.data_ptr()
         env.run_rollout(a)
         if getattr(env, "relief", False):  # the relief pair's budget fault, before GAE and the update
             env.check()                    # read the buffer (the rollout's host sync comes next anyway)
@@ -821,7 +834,8 @@ class BatchedPPO:
             return self._collect_rollout_kernel(slots)
         if (self.use_graphs and hasattr(env, "step_flags") and getattr(env, "_host_reward", None) is None
                 and hasattr(env, "obs") and os.environ.get("BB_ROLLOUT_GRAPH", "1") != "0"):
-            if self._rgraph is None or self._rgraph.key != (id(env), T, n):
+            if (self._rgraph is None or self._rgraph.key != (id(env), T, n)
+                    or (getattr(env, "_log_on", False) and env.log_rows_free() < T)):  # the log history must grow
                 self._rgraph = _RolloutGraph(self, slots)
             return self._rgraph.run(self)
         offs = (C.c_int32 * 21)(*slots)
@@ -1165,9 +1179,18 @@ class BatchedPPO:
         t0 = time.perf_counter()
         start_steps = self.num_timesteps
         iteration = 0
+        logs = bool(getattr(self.env, "_log_on", False))  # the env writes per-episode logs (log_options)
+        if logs:  # room in its device-resident history for this run's rollouts, before any graph holds it
+            per = self.n_envs * self.n_steps * max(self.world, 1)
+            self._log_rows_ahead = -(-max(total - self.num_timesteps, 0) // per) * self.n_steps
+            if self.env.log_rows_free() < self._log_rows_ahead:
+                self._rgraph = None
+                self.env.reserve_log_rows(self._log_rows_ahead, recapture=True)
         while self.num_timesteps < total:
             v0 = self.num_timesteps // max(self.n_envs * self.world, 1)
             self.collect_rollouts()
+            if logs:  # the update boundary: the rollout's host sync has just happened
+                self.env.flush_logs()
             if rollout_callback is not None:
                 rollout_callback(self, v0 + 1, v0 + self.n_steps)
             iteration += 1
@@ -1186,6 +1209,8 @@ class BatchedPPO:
             self.train()
             if callback is not None and callback(self) is False:
                 break
+        if logs:
+            self.env.flush_logs()
         return self
 
     # ------------------------------------------------------------- save/load

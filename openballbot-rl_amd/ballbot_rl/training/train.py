@@ -64,11 +64,15 @@ def experiment_dir(config: Dict[str, Any], out: Optional[str] = None) -> Path:
     return Path("outputs/experiments/runs") / name
 
 
-def make_env(config: Dict[str, Any], num_envs: int, device, seed: int, precision: str = "fp64", stream_seeds=None):
-    """One rank's BallbotVecEnv.  stream_seeds None: every env on np_random(seed)."""
+def make_env(config: Dict[str, Any], num_envs: int, device, seed: int, precision: str = "fp64", stream_seeds=None,
+             log_dir: Optional[str] = None, first_env: int = 0):
+    """One rank's BallbotVecEnv.  stream_seeds None: every env on np_random(seed).  log_dir: where
+    the YAML's `logging` switches (reward_terms, terrain_seeds) write, unless it names a `dir`;
+    None (the eval env): no per-episode logs, as the reference's eval env writes none."""
     from ballbot_gym.envs import BallbotVecEnv
 
-    env_cfg = {"camera": config.get("camera", {}), "env": config.get("env", {}), "logging": config.get("logging", {})}
+    env_cfg = {"camera": config.get("camera", {}), "env": config.get("env", {}),
+               "logging": (config.get("logging", {}) or {}) if log_dir is not None else {}}
     # the reference trains with its depth cameras on (make_ballbot_env(disable_cams=False),
     # training/utils.py:11-20) whenever the config has a camera section
     cams = bool(config.get("camera")) and not config.get("disable_cameras", False)
@@ -76,7 +80,8 @@ def make_env(config: Dict[str, Any], num_envs: int, device, seed: int, precision
                          terrain_config=get_component_config(config, "terrain"), env_config=env_cfg, seed=seed,
                          precision=precision, n_terrains=config.get("n_terrains"), disable_cameras=not cams,
                          stream_seeds=stream_seeds, shared_stream=stream_seeds is None,
-                         reward_compat=str(config.get("reward_compat", "reference")))
+                         reward_compat=str(config.get("reward_compat", "reference")),
+                         log_options={"dir": log_dir} if log_dir is not None else None, first_env=first_env)
 
 
 def main(config: Dict[str, Any], seed: int, out: Optional[str] = None, total_timesteps: Optional[int] = None,
@@ -107,7 +112,9 @@ def main(config: Dict[str, Any], seed: int, out: Optional[str] = None, total_tim
     # with it (train.py:126-141, ballbot_env.py:596); config terrain_streams: shared keeps
     # one np_random(seed) for every env instead
     shared = str(config.get("terrain_streams", "per_env")) == "shared"
-    env = make_env(config, n_local, dev, seed, precision, shard_stream_seeds(seed, first, n_local, per_env=not shared))
+    out_path = experiment_dir(config, out if out is not None else config.get("out"))
+    env = make_env(config, n_local, dev, seed, precision, shard_stream_seeds(seed, first, n_local, per_env=not shared),
+                   log_dir=str(out_path / "env_logs"), first_env=first)
     eval_cfg = config.get("evaluation", {}) or {}
     n_eval = int(eval_cfg.get("n_episodes", 8))
     # the eval VecEnv: N_ENVS envs, env i on np_random(seed + N_ENVS + i) (train.py:90-97);
@@ -116,7 +123,6 @@ def main(config: Dict[str, Any], seed: int, out: Optional[str] = None, total_tim
     eval_env = (make_env(config, n_eval_envs, dev, seed + n_total, precision,
                          shard_stream_seeds(seed + n_total, 0, n_eval_envs, per_env=True)) if rank == 0 else None)
 
-    out_path = experiment_dir(config, out if out is not None else config.get("out"))
     logger = None
     if rank == 0:
         if out_path.exists() and any(out_path.iterdir()):

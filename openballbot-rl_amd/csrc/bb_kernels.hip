@@ -37,6 +37,7 @@
 #include "bb_step.h"
 #include "bb_terrain.h"
 #include "bb_rollout.h"
+#include "bb_episode_log.h"
 #include "bb_render.h"
 #include "bb_ppo.h"
 #include "bb_mlp.h"
@@ -740,7 +741,7 @@ __device__ __forceinline__ void team_policy(const float* __restrict__ P, const i
   }
 }
 
-struct RolloutDev {
+struct RolloutCore {
   const float* P;
   int off[MLP_NSLOTS];
   const float* noise;      // [T][n][3]
@@ -758,6 +759,19 @@ struct RolloutDev {
   double* ep_r;            // [T][n]
   long long* ep_l;         // [T][n]
 };
+// ... and the optional outputs for bb_reward_terms.  (rollout_kernel takes the core by value and
+// these two as a trailing RolloutLog argument that only its LOG instantiation has, so that its
+// launch without them keeps the kernel arguments, and with them the code, it had before.)
+struct RolloutDev : RolloutCore {
+  float* b_tobs;           // [T][n][15] each step's observation before any auto-reset; NULL: not kept
+  uint8_t* b_flags;        // [T][n] each step's done bits; NULL: not kept
+};
+struct RolloutLog {
+  float* tobs;
+  uint8_t* flags;
+};
+__device__ __forceinline__ RolloutLog rollout_log_of() { return RolloutLog{nullptr, nullptr}; }
+__device__ __forceinline__ RolloutLog rollout_log_of(const RolloutLog& l) { return l; }
 
 // One whole PPO rollout (SB3 OnPolicyAlgorithm.collect_rollouts + Monitor) in
 // ONE launch (bb_rollout): every env runs its T steps of (policy, sample,
@@ -773,9 +787,14 @@ struct RolloutDev {
 // identically), and HO = true resumes the parked envs from park[e] -- the
 // policy is fixed during a rollout, so an env's remaining steps need nothing
 // from the other envs.
-template <typename T, bool HO>
-__global__ __launch_bounds__(64) void rollout_kernel(ModelT<T> mg, EnvCfg cfg, Dev d, RolloutDev ro, int L, int epw,
-                                                     int* __restrict__ park) {
+// LG = RolloutLog (one trailing argument): also keep each step's terminal observation and done
+// bits (for bb_reward_terms).  A separate instantiation with its own argument list, so that the
+// launch without them (LG empty) is the kernel it was.
+template <typename T, bool HO, typename... LG>
+__global__ __launch_bounds__(64) void rollout_kernel(ModelT<T> mg, EnvCfg cfg, Dev d, RolloutCore ro, int L, int epw,
+                                                     int* __restrict__ park, LG... lg_arg) {
+  constexpr bool LOG = sizeof...(LG) != 0;
+  const RolloutLog lg = rollout_log_of(lg_arg...);
   extern __shared__ __align__(16) unsigned char smem[];
   const int nwg = int(gridDim.x), b = int(blockIdx.x);
   const int g = (nwg & 7) ? b : (b & 7) * (nwg >> 3) + (b >> 3);
@@ -863,7 +882,9 @@ __global__ __launch_bounds__(64) void rollout_kernel(ModelT<T> mg, EnvCfg cfg, D
 #pragma unroll
       for (int i = 0; i < 15; i++) o_prev[i] = o[i];
     }
-    const int fl = team_step<T, HO>(m, cfg, d, e, tid, q, v, w, step, bk, ac, W, o, r, nullptr, nullptr, 1, tm, cnt);
+    // (a parked step writes no terminal-obs row: the finish launch redoes it and writes it then)
+    const int fl = team_step<T, HO>(m, cfg, d, e, tid, q, v, w, step, bk, ac, W, o, r,
+                                    LOG ? lg.tobs + 15 * row : nullptr, nullptr, 1, tm, cnt);
     if (!HO && (fl & F_PARKED)) {  // team-uniform: the env resumes at step t in the finish launch
 #pragma unroll
       for (int i = 0; i < 15; i++) o[i] = o_prev[i];
@@ -878,6 +899,7 @@ __global__ __launch_bounds__(64) void rollout_kernel(ModelT<T> mg, EnvCfg cfg, D
       ro.b_rew[row] = r;
       ro.ep_r[row] = dn ? ret : __builtin_nan("");
       ro.ep_l[row] = dn ? len : 0;
+      if constexpr (LOG) lg.flags[row] = uint8_t(fl);
     }
     ret = dn ? 0.0 : ret;
     len = dn ? 0 : len;
@@ -1118,7 +1140,8 @@ constexpr int QW = 4, QENV = 4 * QW;
 // claimed env runs one (policy, sample, clip, step, bookkeeping) step as
 // rollout_kernel does; its observation and episode counters wait in LDS
 // between claims.
-template <typename T, bool RO>
+// LOG (with RO): also the terminal observations and done bits (rollout_kernel's LOG).
+template <typename T, bool RO, bool LOG = false>
 __global__ __launch_bounds__(64 * QW) void relief_multi_kernel(ModelT<T> mg, EnvCfg cfg, Dev d,
                                                                const float* __restrict__ act, int K,
                                                                float* __restrict__ obs, float* __restrict__ rew,
@@ -1249,7 +1272,8 @@ __global__ __launch_bounds__(64 * QW) void relief_multi_kernel(ModelT<T> mg, Env
         a[0] = ak[0]; a[1] = ak[1]; a[2] = ak[2];
       }
       const int fl = team_step<T>(m, cfg, d, e, tid, W.qn, W.vn, W.wn, step, bk, a, W, o, r,
-                                  (!RO && tobs) ? tobs + 15 * row : nullptr, (!RO && pos2d) ? pos2d + 2 * row : nullptr,
+                                  LOG ? ro.b_tobs + 15 * row : ((!RO && tobs) ? tobs + 15 * row : nullptr),
+                                  (!RO && pos2d) ? pos2d + 2 * row : nullptr,
                                   RO ? 1 : auto_reset, tm, s_cnt[i], full);
       if (lead) {
         if (RO) {  // collect_rollouts + Monitor bookkeeping (bb_rollout_track)
@@ -1259,6 +1283,7 @@ __global__ __launch_bounds__(64 * QW) void relief_multi_kernel(ModelT<T> mg, Env
           ro.b_rew[row] = r;
           ro.ep_r[row] = dn ? ret : __builtin_nan("");
           ro.ep_l[row] = dn ? len : 0;
+          if constexpr (LOG) ro.b_flags[row] = uint8_t(fl);
           s_ret[i] = dn ? 0.0 : ret;
           s_len[i] = dn ? 0 : len;
           s_start[i] = dn ? 1 : 0;
@@ -1392,7 +1417,8 @@ struct RollCarry {
 // runs the policy on the env's observation (team_policy), samples and clips the action, steps,
 // and keeps the rollout buffer and the Monitor's episode statistics (rollout_kernel's body);
 // K is the rollout length, act and the [K][n] outputs are unused.
-template <typename T, bool FULL, bool ROLL>
+// LOG (with ROLL): also the terminal observations and done bits (rollout_kernel's LOG).
+template <typename T, bool FULL, bool ROLL, bool LOG = false>
 __device__ __forceinline__ void pair_loop(const ModelT<T>& mg, const EnvCfg& cfg, const Dev& d, const float* __restrict__ act,
                                           int K, float* __restrict__ obs, float* __restrict__ rew,
                                           uint8_t* __restrict__ done, float* __restrict__ tobs,
@@ -1523,8 +1549,11 @@ __device__ __forceinline__ void pair_loop(const ModelT<T>& mg, const EnvCfg& cfg
         a[0] = ak[0]; a[1] = ak[1]; a[2] = ak[2];
       }
       float o[15], r;
+      // (LOG: a rollout keeps the terminal obs in its own buffer; a step the fast loop hands over
+      // writes no row -- the full loop redoes it and writes it then)
+      float* const trow = LOG ? ro.b_tobs : tobs;
       const int fl = team_step<T, FULL, FULL>(m, cfg, d, e, tid, W.qn, W.vn, W.wn, step, bk, a, W, o, r,
-                                               tobs ? tobs + 15 * row : nullptr, pos2d ? pos2d + 2 * row : nullptr,
+                                               trow ? trow + 15 * row : nullptr, pos2d ? pos2d + 2 * row : nullptr,
                                                auto_reset, tm, cnt);
       int next = kind;
       if (!FULL && (fl & F_PARKED)) {  // the fast path handed the step over: the full launch redoes it
@@ -1540,6 +1569,7 @@ __device__ __forceinline__ void pair_loop(const ModelT<T>& mg, const EnvCfg& cfg
           ro.b_rew[row] = r;
           ro.ep_r[row] = dn ? ret : __builtin_nan("");
           ro.ep_l[row] = dn ? len : 0;
+          if constexpr (LOG) ro.b_flags[row] = uint8_t(fl);
           c.ret = dn ? 0.0 : ret;
           c.len = dn ? 0 : len;
           c.start = dn ? 1 : 0;
@@ -1635,7 +1665,7 @@ __global__ __launch_bounds__(64) void relief_pair_kernel(ModelT<T> mg, EnvCfg cf
 // loop, interleaved by groups of NXCD blocks (pair_kind_of); the two loops are disjoint regions
 // of the kernel, so it keeps the larger one's registers, not their union.  ROLL: a rollout
 // (bb_rollout on relief banks; ro), K = ro.T
-template <typename T, bool ROLL>
+template <typename T, bool ROLL, bool LOG = false>
 __global__ __launch_bounds__(64) void relief_pair1_kernel(ModelT<T> mg, EnvCfg cfg, Dev d, const float* __restrict__ act,
                                                           int K, float* __restrict__ obs, float* __restrict__ rew,
                                                           uint8_t* __restrict__ done, float* __restrict__ tobs,
@@ -1652,11 +1682,11 @@ __global__ __launch_bounds__(64) void relief_pair1_kernel(ModelT<T> mg, EnvCfg c
   __shared__ int s_diag[WAVE / TEAM][3];
   __shared__ RollCarry s_roll[ROLL ? WAVE / TEAM : 1];
   if (kind == 0)
-    pair_loop<T, false, ROLL>(mg, cfg, d, act, K, obs, rew, done, tobs, pos2d, auto_reset, seg, budget, gate, wg, smem,
-                              ms, s_cnt, s_diag, ro, s_roll);
+    pair_loop<T, false, ROLL, LOG>(mg, cfg, d, act, K, obs, rew, done, tobs, pos2d, auto_reset, seg, budget, gate, wg,
+                                   smem, ms, s_cnt, s_diag, ro, s_roll);
   else
-    pair_loop<T, true, ROLL>(mg, cfg, d, act, K, obs, rew, done, tobs, pos2d, auto_reset, seg, budget, gate, wg, smem,
-                             ms, s_cnt, s_diag, ro, s_roll);
+    pair_loop<T, true, ROLL, LOG>(mg, cfg, d, act, K, obs, rew, done, tobs, pos2d, auto_reset, seg, budget, gate, wg,
+                                  smem, ms, s_cnt, s_diag, ro, s_roll);
 }
 
 // before the pair: every env's first route (predict_kernel's test) into the
@@ -1989,6 +2019,10 @@ int launch_rollout(bb_handle* h, const RolloutDev& ro, hipStream_t s) {
   const int epw = h->epw;
   const int blocks = (h->n + epw - 1) / epw;
   const int route = h->route >= 0 ? h->route : (h->n_relief == 0 ? 1 : 0);
+  // with the terminal-obs / flag buffers attached: the LOG instantiations (the others are unchanged)
+  const bool lg = ro.b_tobs != nullptr;
+  const RolloutCore& core = ro;
+  const RolloutLog rl{ro.b_tobs, ro.b_flags};
   if (route == 0 && h->team == 16 && h->multi_queue && h->pair && h->pair_one) {
     // relief banks: the relief pair with the policy in it (pair_loop<.., ROLL>)
     if (bb_pair_launch_tu(h, sizeof(T) == 8, nullptr, ro.T, nullptr, nullptr, nullptr, nullptr, nullptr, 1, s, nullptr,
@@ -1996,18 +2030,29 @@ int launch_rollout(bb_handle* h, const RolloutDev& ro, hipStream_t s) {
       return fail("bb_rollout: relief pair launch failed");
   } else if (route == 0 && h->team == 16 && h->multi_queue) {  // relief banks: the work queue with the policy in it
     const Dev dq = balanced_dev(h, s);
-    hipLaunchKernelGGL((relief_multi_kernel<T, true>), dim3((h->n + QENV - 1) / QENV), dim3(64 * QW),
+    auto* const kq = lg ? relief_multi_kernel<T, true, true> : relief_multi_kernel<T, true, false>;
+    hipLaunchKernelGGL(kq, dim3((h->n + QENV - 1) / QENV), dim3(64 * QW),
                        relief_lds_bytes<T>(), s, model_of<T>(h), h->cfg, dq, (const float*)nullptr, ro.T,
                        (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr, (float*)nullptr, (float*)nullptr, 1, ro,
                        (const int*)nullptr);
   } else if (h->multi_park) {  // the fast steps, then the parked envs' hand-overs and the rest of their steps
-    hipLaunchKernelGGL((rollout_kernel<T, false>), dim3(blocks), dim3(WAVE), rollout_lds_bytes<T>(epw), s,
-                       model_of<T>(h), h->cfg, h->d, ro, h->team, epw, h->d.park);
+    if (lg) {
+      hipLaunchKernelGGL((rollout_kernel<T, false, RolloutLog>), dim3(blocks), dim3(WAVE), rollout_lds_bytes<T>(epw), s,
+                         model_of<T>(h), h->cfg, h->d, core, h->team, epw, h->d.park, rl);
+      hipLaunchKernelGGL((rollout_kernel<T, true, RolloutLog>), dim3(blocks), dim3(WAVE), rollout_lds_bytes<T>(epw), s,
+                         model_of<T>(h), h->cfg, h->d, core, h->team, epw, h->d.park, rl);
+    } else {
+      hipLaunchKernelGGL((rollout_kernel<T, false>), dim3(blocks), dim3(WAVE), rollout_lds_bytes<T>(epw), s,
+                         model_of<T>(h), h->cfg, h->d, core, h->team, epw, h->d.park);
+      hipLaunchKernelGGL((rollout_kernel<T, true>), dim3(blocks), dim3(WAVE), rollout_lds_bytes<T>(epw), s,
+                         model_of<T>(h), h->cfg, h->d, core, h->team, epw, h->d.park);
+    }
+  } else if (lg)
+    hipLaunchKernelGGL((rollout_kernel<T, true, RolloutLog>), dim3(blocks), dim3(WAVE), rollout_lds_bytes<T>(epw), s,
+                       model_of<T>(h), h->cfg, h->d, core, h->team, epw, (int*)nullptr, rl);
+  else
     hipLaunchKernelGGL((rollout_kernel<T, true>), dim3(blocks), dim3(WAVE), rollout_lds_bytes<T>(epw), s,
-                       model_of<T>(h), h->cfg, h->d, ro, h->team, epw, h->d.park);
-  } else
-    hipLaunchKernelGGL((rollout_kernel<T, true>), dim3(blocks), dim3(WAVE), rollout_lds_bytes<T>(epw), s,
-                       model_of<T>(h), h->cfg, h->d, ro, h->team, epw, (int*)nullptr);
+                       model_of<T>(h), h->cfg, h->d, core, h->team, epw, (int*)nullptr);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -2025,7 +2070,8 @@ int launch_pair(bb_handle* h, const float* a, int K, float* o, float* r, uint8_t
                      h->pair_heavy_pct);
   hipLaunchKernelGGL(pair_rings_kernel, dim3(1), dim3(64), 0, s, h->d, gate);
   if (ro) {  // a rollout: the one-launch form (launch_rollout only comes here with pair_one)
-    hipLaunchKernelGGL((relief_pair1_kernel<T, true>), dim3(h->pair_cap), dim3(WAVE), plb, s, m, h->cfg, h->d,
+    auto* const kp = ro->b_tobs ? relief_pair1_kernel<T, true, true> : relief_pair1_kernel<T, true, false>;
+    hipLaunchKernelGGL(kp, dim3(h->pair_cap), dim3(WAVE), plb, s, m, h->cfg, h->d,
                        (const float*)nullptr, ro->T, (float*)nullptr, (float*)nullptr, (uint8_t*)nullptr,
                        (float*)nullptr, (float*)nullptr, 1, h->pair_seg, h->pair_budget, gate, *ro);
   } else if (h->pair_one) {
@@ -2068,8 +2114,9 @@ extern "C" __attribute__((visibility("hidden"))) int bb_pair_setup_tu(int fp64, 
 template <typename T>
 int pair_setup(int* per_cu) {  // -> a hipError_t (this unit's error text is not the C-ABI's)
   const size_t plb = multi_lds_bytes<T>(4);
-  const void* ks[4] = {(const void*)relief_pair1_kernel<T, false>, (const void*)relief_pair_kernel<T, false>,
-                       (const void*)relief_pair_kernel<T, true>, (const void*)relief_pair1_kernel<T, true>};
+  const void* ks[5] = {(const void*)relief_pair1_kernel<T, false>, (const void*)relief_pair_kernel<T, false>,
+                       (const void*)relief_pair_kernel<T, true>, (const void*)relief_pair1_kernel<T, true>,
+                       (const void*)relief_pair1_kernel<T, true, true>};
   for (const void* k : ks) {
     const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, int(plb));
     if (e != hipSuccess) return int(e);
@@ -2078,6 +2125,9 @@ int pair_setup(int* per_cu) {  // -> a hipError_t (this unit's error text is not
   int nb = 0, nr = 0;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ks[0], WAVE, plb);
   if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nr, ks[3], WAVE, plb);
+  int nl = 0;  // ... and the rollout's form that keeps the terminal observations
+  if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nl, ks[4], WAVE, plb);
+  nr = nr < nl ? nr : nl;
   *per_cu = nb < nr ? nb : nr;
   return int(e);
 }
@@ -2401,14 +2451,20 @@ int bb_create(int n_envs, int device, const bb_params* p, bb_handle** out) {
                                  : (const void*)multi_step_kernel<float, true>};
     for (const void* k : mk) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mlb));
     const int rlb = (int)(h->fp64 ? rollout_lds_bytes<double>(h->epw) : rollout_lds_bytes<float>(h->epw));
-    const void* rk[2] = {h->fp64 ? (const void*)rollout_kernel<double, false> : (const void*)rollout_kernel<float, false>,
-                         h->fp64 ? (const void*)rollout_kernel<double, true> : (const void*)rollout_kernel<float, true>};
+    const void* rk[4] = {h->fp64 ? (const void*)rollout_kernel<double, false> : (const void*)rollout_kernel<float, false>,
+                         h->fp64 ? (const void*)rollout_kernel<double, true> : (const void*)rollout_kernel<float, true>,
+                         h->fp64 ? (const void*)rollout_kernel<double, false, RolloutLog>
+                                 : (const void*)rollout_kernel<float, false, RolloutLog>,
+                         h->fp64 ? (const void*)rollout_kernel<double, true, RolloutLog>
+                                 : (const void*)rollout_kernel<float, true, RolloutLog>};
     for (const void* k : rk) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, rlb));
     const int qlb = (int)(h->fp64 ? relief_lds_bytes<double>() : relief_lds_bytes<float>());
-    const void* qk[2] = {h->fp64 ? (const void*)relief_multi_kernel<double, false>
+    const void* qk[3] = {h->fp64 ? (const void*)relief_multi_kernel<double, false>
                                  : (const void*)relief_multi_kernel<float, false>,
                          h->fp64 ? (const void*)relief_multi_kernel<double, true>
-                                 : (const void*)relief_multi_kernel<float, true>};
+                                 : (const void*)relief_multi_kernel<float, true>,
+                         h->fp64 ? (const void*)relief_multi_kernel<double, true, true>
+                                 : (const void*)relief_multi_kernel<float, true, true>};
     for (const void* k : qk) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, qlb));
     // (the relief pair's kernels get theirs in their own unit: bb_pair_setup_tu)
   }
@@ -2754,6 +2810,8 @@ int bb_rollout(bb_handle* h, const bb_rollout_args* a, void* stream) {
       !a->ep_l_out)
     return fail("bb_rollout: NULL argument");
   if (a->n_steps < 1) return fail("bb_rollout: n_steps must be >= 1 (got %d)", a->n_steps);
+  if (!a->buf_terminal_obs != !a->buf_flags)
+    return fail("bb_rollout: buf_terminal_obs and buf_flags go together (both, or both NULL)");
   if (h->cfg.reward_kind == BB_REWARD_NONE)
     return fail("bb_rollout: the reward is a host-side plugin (BB_REWARD_NONE); step with bb_step instead");
   const int sizes[MLP_NSLOTS] = {128 * 15, 128 * 128, 128 * 128, 128 * 128, 128, 128, 128, 128,
@@ -2771,7 +2829,26 @@ int bb_rollout(bb_handle* h, const bb_rollout_args* a, void* stream) {
   ro.ep_len = reinterpret_cast<long long*>(a->ep_len); ro.b_obs = a->buf_obs; ro.b_act = a->buf_actions;
   ro.b_val = a->buf_values; ro.b_logp = a->buf_log_prob; ro.b_rew = a->buf_rewards; ro.b_starts = a->buf_starts;
   ro.ep_r = a->ep_r_out; ro.ep_l = reinterpret_cast<long long*>(a->ep_l_out);
+  ro.b_tobs = a->buf_terminal_obs; ro.b_flags = a->buf_flags;
   return h->fp64 ? launch_rollout<double>(h, ro, (hipStream_t)stream) : launch_rollout<float>(h, ro, (hipStream_t)stream);
+}
+
+int bb_reward_terms(bb_handle* h, const float* obs, const uint8_t* flags, int k, float* terms, int64_t terms_rows,
+                    int64_t* book, void* stream) {
+  // argument checks first (none of them touches the handle or HIP)
+  if (!obs || !flags || !terms || !book) return fail("bb_reward_terms: NULL argument");
+  if (k < 1) return fail("bb_reward_terms: k_steps must be >= 1 (got %d)", k);
+  if (terms_rows < 0) return fail("bb_reward_terms: terms_rows must be >= 0 (got %lld)", (long long)terms_rows);
+  if (!h) return fail("bb_reward_terms: NULL handle");
+  if (h->cfg.reward_kind != BB_REWARD_DIRECTIONAL)
+    return fail("bb_reward_terms: the handle's reward is not BB_REWARD_DIRECTIONAL (kind %d): the reference logs "
+                "the directional reward's terms only",
+                h->cfg.reward_kind);
+  const RewardTermsCfg rc{{h->cfg.target[0], h->cfg.target[1]}, h->cfg.reward_scale, h->cfg.action_reg_coef};
+  if (launch_reward_terms(rc, obs, flags, k, h->n, terms, (long long)terms_rows, reinterpret_cast<long long*>(book),
+                          (hipStream_t)stream))
+    return fail("bb_reward_terms: launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
 }
 
 int bb_get_state(bb_handle* h, double* qpos, double* qvel, double* warm, int32_t* steps) {

@@ -42,6 +42,9 @@ def main():
                     help="EvalCallback every N vec-env steps (the reference: 5000) on an eval VecEnv of --envs envs, "
                          "env i on np_random(seed + envs + i); writes <out>/results/evaluations.npz")
     ap.add_argument("--eval-episodes", type=int, default=8)
+    ap.add_argument("--log-reward-terms", type=int, default=0, metavar="K",
+                    help="per-episode logs on (log_options reward_terms): the recorder runs for every env, the first K "
+                         "envs write files under <out>/env_logs (DESIGN §7c: the cost when on)")
     a = ap.parse_args()
 
     import torch
@@ -54,8 +57,13 @@ def main():
     from ballbot_rl.training.ppo import BatchedPPO
     from ballbot_rl.training.schedules import lr_schedule
 
+    log = None
+    if a.log_reward_terms:
+        log = {"reward_terms": True, "envs": list(range(min(a.log_reward_terms, a.envs))),
+               "dir": str(Path(a.out) / "env_logs") if a.out else None}
     env = BallbotVecEnv(a.envs, device="cuda:0", precision=a.precision, seed=a.seed,
-                        terrain_config={"type": a.terrain, "config": {}}, disable_cameras=not a.cameras)
+                        terrain_config={"type": a.terrain, "config": {}}, disable_cameras=not a.cameras,
+                        log_options=log)
     frozen, pre_s = None, 0.0
     if a.cameras and a.frozen_encoder:
         from ballbot_rl.encoders import TinyAutoencoder, collect_depth_images, train_autoencoder
@@ -131,7 +139,8 @@ def main():
            "kl_stops": getattr(m, "kl_stops", None),
            "config": {"envs": a.envs, "n_steps": a.n_steps, "batch_size": a.batch, "n_epochs": a.epochs,
                       "terrain": a.terrain, "precision": a.precision, "cameras": a.cameras,
-                      "frozen_encoder": frozen is not None, "encoder_pretrain_s": pre_s},
+                      "frozen_encoder": frozen is not None, "encoder_pretrain_s": pre_s,
+                      "log_reward_terms": a.log_reward_terms},
            "ep_rew_mean": _eprew(m), "ep_len_mean": _eplen(m), "env_stats": env.stats()}
     print(json.dumps(out), flush=True)
     env.close()
