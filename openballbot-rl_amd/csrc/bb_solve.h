@@ -380,17 +380,51 @@ struct LineSearch {
   BB_HD T fallback() const { return lo > 0 ? lo : (hi > 0 ? hi * dlo / (dlo - dhi) : T(0)); }
 };
 
+// What solve_team carries across its Newton iterations, as mj_solPrimal does:
+// every contact's jar = J a - aref and M a.  Computed from the warm start once
+// per solve; after each step a += alpha s they become jar + alpha J s and
+// M a + alpha M s, from the line search's own J s and M s.
+template <typename T>
+struct SolveCarry {
+  T jar[3 + MAXG][3];
+  T Ma[NV];
+};
+
 // Newton on f(a) (mj_solNewton).  a: warm start in, qacc out (replicated in
 // every lane of the team).  Returns the iteration count (team-uniform).
 // Host / reference path (tests/hostcheck): wheel and ball-hfield contacts
 // only; the GPU solve (bb_team16.h) also handles the base-tree contacts.
+// carry (optional): the carried jar and M a as they stand at exit.
+// The carry here covers every contact and every row.  Neither GPU form does
+// exactly that: the fast kernels' solve16 carries each lane's first-round
+// contact (the first 16 of 3 + ng) and the row's M a - qfs and rebuilds later
+// rounds' jar from a; the full kernel's solve16 carries nothing and recomputes
+// from a in every iteration, as this function did before (registers,
+// bb_team16.h).  The three agree to rounding, not in the order of operations.
 template <typename T>
-BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T* a, const Team& tm) {
+BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T* a, const Team& tm,
+                     SolveCarry<T>* carry = nullptr) {
   const Mass<T>& M = W.M;
   PH_DECL
   const T mu_w = m.fr_wheel[0], f1w = m.fr_wheel[0], f2w = m.fr_wheel[1];
   const int nc = 3 + ng;
   T hd[NV];  // Hessian diagonal before factorisation (pivot floor)
+  SolveCarry<T> cy;  // host / reference path: plenty of stack
+  team_sync();
+  for (int c = tm.tl; c < nc; c += tm.L) {
+    if (c < 3) {
+      const WheelCon<T>& C = W.wc[c];
+#pragma unroll
+      for (int r = 0; r < 3; r++) cy.jar[c][r] = wheel_dot(C, c, r, a) - C.aref[r];
+    } else {
+      T J[3][6], ar[3], D;
+      ground_contact(m, W.g + (c - 3) * NGF, W.P.RB, W.vi, J, ar, D);
+#pragma unroll
+      for (int r = 0; r < 3; r++) cy.jar[c][r] = ground_dot(J, r, a) - ar[r];
+    }
+  }
+  mass_mul(M, a, cy.Ma);
+  T* const Ma = cy.Ma;
   int it = 0;
   bool held = false;  // the improvement stop was overridden once (IMPR_GRAD, bb_physics.h)
   for (; it < m.maxiter; it++) {
@@ -404,9 +438,8 @@ BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T*
     for (int c = tm.tl; c < nc; c += tm.L) {
       if (c < 3) {
         const WheelCon<T>& C = W.wc[c];
-        T jar[3], f[3], Cc[6];
-#pragma unroll
-        for (int r = 0; r < 3; r++) jar[r] = wheel_dot(C, c, r, a) - C.aref[r];
+        T f[3], Cc[6];
+        const T* jar = cy.jar[c];  // carried
         T Dw[3] = {C.D[0], C.D[1], C.D[2]};
         cone_eval(jar, mu_w, f1w, f2w, Dw, f, Cc);
 #pragma unroll
@@ -421,9 +454,7 @@ BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T*
         const T* gc = W.g + (c - 3) * NGF;
         T J[3][6], ar[3], D;
         ground_contact(m, gc, W.P.RB, W.vi, J, ar, D);
-        T jar[3];
-#pragma unroll
-        for (int r = 0; r < 3; r++) jar[r] = ground_dot(J, r, a) - ar[r];
+        const T* jar = cy.jar[c];  // carried
         T Dv[3] = {D, D, D}, f[3], Cc[6];
         cone_eval(jar, T(1), T(1), T(1), Dv, f, Cc);
         T w[3][6];
@@ -453,8 +484,7 @@ BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T*
     team_sync();
     PH(1)
     // ---- (3) gradient, replicated: g = M a - qfs - sum_c J_c' f_c
-    T g[NV], Ma[NV];
-    mass_mul(M, a, Ma);
+    T g[NV];  // Ma: carried
 #pragma unroll
     for (int i = 0; i < NV; i++) g[i] = Ma[i] - qfs[i];
 #pragma unroll
@@ -528,20 +558,22 @@ BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T*
 #pragma unroll
     for (int i = 0; i < NV; i++) { sMs += s[i] * Ms[i]; gs += s[i] * (Ma[i] - qfs[i]); }
     LsTerm<T> lst[3 + MAXG];  // line-search terms (host / reference path: plenty of stack)
+    T xs[3 + MAXG][3];        // J s of every contact
     const T kdw = T(1) / (mu_w * mu_w * (1 + mu_w * mu_w));
     for (int c = tm.tl; c < nc; c += tm.L) {
-      T j0[3], x[3];
+      const T* j0 = cy.jar[c];  // carried
+      T* x = xs[c];
       if (c < 3) {
         const WheelCon<T>& C = W.wc[c];
 #pragma unroll
-        for (int r = 0; r < 3; r++) { j0[r] = wheel_dot(C, c, r, a) - C.aref[r]; x[r] = wheel_dot(C, c, r, s); }
+        for (int r = 0; r < 3; r++) x[r] = wheel_dot(C, c, r, s);
         lst[c].prep(j0, x, mu_w, f1w, f2w, C.D, C.D[0] * kdw);
       } else {
         const T* gc = W.g + (c - 3) * NGF;
         T J[3][6], ar[3], D;
         ground_contact(m, gc, W.P.RB, W.vi, J, ar, D);
 #pragma unroll
-        for (int r = 0; r < 3; r++) { j0[r] = ground_dot(J, r, a) - ar[r]; x[r] = ground_dot(J, r, s); }
+        for (int r = 0; r < 3; r++) x[r] = ground_dot(J, r, s);
         const T Dv[3] = {D, D, D};
         lst[c].prep(j0, x, T(1), T(1), T(1), Dv, D * T(0.5));
       }
@@ -603,6 +635,12 @@ BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T*
     T sn = 0, an2 = 0;
 #pragma unroll
     for (int i = 0; i < NV; i++) { a[i] += alpha * s[i]; sn += s[i] * s[i]; an2 += a[i] * a[i]; }
+    // jar and M a follow a along s
+    for (int c = tm.tl; c < nc; c += tm.L)
+#pragma unroll
+      for (int r = 0; r < 3; r++) cy.jar[c][r] += alpha * xs[c][r];
+#pragma unroll
+    for (int i = 0; i < NV; i++) Ma[i] += alpha * Ms[i];
     PH(6)
     if (alpha * alpha * sn <= T(1e-30) + m.step_rel2 * (1 + an2)) { it++; break; }
     // MuJoCo's improvement stop (mj_solPrimal: scale * (oldcost - cost) < tolerance)
@@ -614,6 +652,7 @@ BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T*
   }
   PH(7)
   PH_FLUSH(tm)
+  if (carry) *carry = cy;
   return it;
 }
 

@@ -425,15 +425,16 @@ __device__ __forceinline__ void ls_term(const ModelT<T>& m, const EnvWork<T>& W,
 //                  c < GC_LDS (the BODY-only W.bc region and the mass blocks,
 //                  dead during the solve); later contacts (rare: more than 13)
 //                  and the full kernel's rebuild them per use
-//   contact pass   wheel lanes publish C J and f (LDS); ground lanes add their
-//                  ball-block gradient and C-weighted J'J partials; base-tree
+//   contact pass   from the carried jar of the lane's first contact (fast kernels:
+//                  computed from a in the first iteration only); wheel lanes publish
+//                  C and f (LDS); ground lanes add their ball-block gradient
+//                  and C-weighted J'J partials; base-tree
 //                  contacts (full kernel) are rebuilt by one lane each and
 //                  broadcast (DPP) so that every lane adds its own Hessian row
 //                  and gradient entry
 //   gradient       lane i: g_i = (M a)_i - qfs_i - sum_w J_w[:,i]' f_w from its
-//                  dense M row and the wheel data, plus the team-summed
-//                  ball-block ground part: 6 + 21 team sums (all-replicated
-//                  gradient: 15 + 21)
+//                  dense M row (carried with jar) and the wheel data, plus the
+//                  team-summed ball-block ground part: 6 + 21 team sums
 //   line search    s'M s and s'(M a - qfs) from the rows (team sums, no
 //                  replicated mass products); each contact term from the
 //                  contact pass's jar and the stored Jacobian
@@ -487,6 +488,14 @@ __device__ __forceinline__ void ground_get(const ModelT<T>& m, EnvWork<T>& W, in
   }
 }
 
+// -DBB_NO_CARRY (A/B builds, tools/build_variant.sh): the fast kernels' solve recomputes jar and
+// M a from a in every Newton iteration, as the full kernel's does.
+#ifndef BB_NO_CARRY
+constexpr bool kCarry = true;
+#else
+constexpr bool kCarry = false;
+#endif
+
 template <bool BODY, bool FUSE = false, typename T>
 __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, int tl) {
   if constexpr (!BODY) nb = 0;
@@ -502,7 +511,10 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
   // scratch).  Publishing the ball-terrain contacts' the same way for the
   // ball-row owners was measured and dropped: the per-contact LDS loop on the
   // row lanes exposes its latency (flat 0.808 ms/step against 0.666 with the
-  // ball-block team sums)
+  // ball-block team sums).  A second form kept C J and f in the contact's lane
+  // and read only the row's own column of J from LDS, the other factor arriving
+  // inside v_fmac_f64_dpp: no gain on the 500-step line, slower in the driver
+  // window, 16 B of scratch in multi_step_kernel<double, false>.
   static_assert(offsetof(typename EnvWork<T>::U, hes.hg) == offsetof(typename EnvWork<T>::U, hes.wf) + 9 * sizeof(T),
                 "wheel f/C scratch needs wf and hg adjacent");
   T* const wCf = &W.u.hes.wf[0][0];
@@ -518,6 +530,18 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
 #define BB_HROW(k) W.H[hidx(row, k)]
 #endif
   PH_DECL
+  // carried across the Newton iterations, as in mj_solPrimal: this lane's first-round contact's
+  // jar = J a - aref (c == tl) and this row's (M a)_i.  The line search of an iteration holds
+  // x = J s and (M s)_i for the same contact and row, and a += alpha s makes them jar + alpha x
+  // and Ma + alpha Ms.  Computed from a in the first iteration of a solve only, from the warm
+  // start, where every iteration computed them before (-DBB_NO_CARRY: in every iteration); mq =
+  // Ma - qfs is what the row keeps.  Contacts of later rounds (c >= 16) are rebuilt from a at every use.
+  // The fast kernels only, FUSE or not, floats and doubles (every launch form steps an env through
+  // the same fast and full code, so the forms still agree bit for bit): the full kernel's solve,
+  // at the 512-register limit, spills with the loop-carried values (step_kernel<double, true>:
+  // 16 -> 548 B of scratch, also with them parked in LDS across the line search); it recomputes.
+  constexpr bool CARRY = kCarry && !BODY;
+  T jar0[3] = {0, 0, 0}, mq = 0;
   int it = 0;
   bool held = false;  // the improvement stop was overridden once (IMPR_GRAD, bb_physics.h)
   for (; it < m.maxiter; it++) {
@@ -528,73 +552,91 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     // them to VGPR lanes, and every use costs two v_readlane and a hazard wait (flat -1.2%)
     int tlx = tl;
     asm volatile("" : "+v"(tlx));
+    const bool fresh = !CARRY || it == 0;  // jar and M a from a
     // ---- (1) contact pass, contact-parallel (c = tl, tl + 16, ...): the
     // wheels' cone force f and Hessian C (3x3, packed) into LDS for the row
     // owners; ball-terrain contacts add ball-block gradient and C-weighted J'J
-    // partials for team sums
+    // partials for team sums.  In force-inlined pieces: as one loop body the
+    // register-limited kernels spill more with the carried values
     T gg[6], Hg[21];
-#pragma unroll
-    for (int i = 0; i < 6; i++) gg[i] = 0;
-#pragma unroll
-    for (int i = 0; i < 21; i++) Hg[i] = 0;
-    T jar0[3] = {0, 0, 0};  // this lane's first contact, kept for the line search
-#ifdef BB_EXP_DUP_CPASS  // timing experiment: the wheel / ball-terrain contact pass twice
-    for (int rep = 0; rep < 2; rep++) {
-      if (rep == 1) {
-        T z = 0;
-        for (int i = 0; i < 6; i++) z += gg[i];
-        for (int i = 0; i < 21; i++) z += Hg[i];
-        asm volatile("" :: "v"(z) : "memory");
-        for (int i = 0; i < 6; i++) gg[i] = 0;
-        for (int i = 0; i < 21; i++) Hg[i] = 0;
-        team_sync();
-      }
-#endif
-    for (int c = tl; c < ngc; c += L) {
-      const bool wheel = c < 3;
-      T jar[3], Dc = 0, Jg[3][6];
-      if (wheel) {
-#pragma unroll
-        for (int r = 0; r < 3; r++) jar[r] = wheel_dot(W.wc[c], c, r, a) - W.wc[c].aref[r];
-      } else {
-        T ar[3];
-        ground_get<BODY>(m, W, c - 3, Jg, ar, Dc);
-#pragma unroll
-        for (int r = 0; r < 3; r++) jar[r] = ground_dot(Jg, r, a) - ar[r];
-      }
-      if (c == tl) {
-#pragma unroll
-        for (int r = 0; r < 3; r++) jar0[r] = jar[r];
-      }
+    // cone force and Hessian of wheel or ball-terrain contact c from its jar
+    auto cone_of = [&](bool wheel, int c, const T (&jar)[3], T Dc, T (&f)[3], T (&Cc)[6]) __attribute__((always_inline)) {
       const T D[3] = {wheel ? W.wc[c].D[0] : Dc, wheel ? W.wc[c].D[1] : Dc, wheel ? W.wc[c].D[2] : Dc};
       const T mu = wheel ? muw : T(1), f1 = wheel ? muw : T(1), f2 = wheel ? m.fr_wheel[1] : T(1);
       const T Dm = D[0] * (wheel ? kdw : T(0.5));  // 1 / (mu^2 (1 + mu^2))
-      T f[3], Cc[6];
       cone_sel(jar, mu, f1, f2, D, Dm, f, Cc);
-      if (wheel) {
-        T* p = wCf + 9 * c;
+    };
+    auto wheel_put = [&](int c, const T (&f)[3], const T (&Cc)[6]) __attribute__((always_inline)) {
+      T* p = wCf + 9 * c;
 #pragma unroll
-        for (int r = 0; r < 6; r++) p[r] = Cc[r];
+      for (int r = 0; r < 6; r++) p[r] = Cc[r];
 #pragma unroll
-        for (int r = 0; r < 3; r++) p[6 + r] = f[r];
-      } else {
-        T w[3][6];
+      for (int r = 0; r < 3; r++) p[6 + r] = f[r];
+    };
+    auto cj_of = [&](const T (&Cc)[6], const T (&Jg)[3][6], T (&w)[3][6]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < 6; i++) {
-          gg[i] -= Jg[0][i] * f[0] + Jg[1][i] * f[1] + Jg[2][i] * f[2];
-          w[0][i] = Cc[0] * Jg[0][i] + Cc[3] * Jg[1][i] + Cc[4] * Jg[2][i];
-          w[1][i] = Cc[3] * Jg[0][i] + Cc[1] * Jg[1][i] + Cc[5] * Jg[2][i];
-          w[2][i] = Cc[4] * Jg[0][i] + Cc[5] * Jg[1][i] + Cc[2] * Jg[2][i];
-        }
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-          for (int j = 0; j <= i; j++) Hg[i * (i + 1) / 2 + j] += Jg[0][i] * w[0][j] + Jg[1][i] * w[1][j] + Jg[2][i] * w[2][j];
+      for (int i = 0; i < 6; i++) {
+        w[0][i] = Cc[0] * Jg[0][i] + Cc[3] * Jg[1][i] + Cc[4] * Jg[2][i];
+        w[1][i] = Cc[3] * Jg[0][i] + Cc[1] * Jg[1][i] + Cc[5] * Jg[2][i];
+        w[2][i] = Cc[4] * Jg[0][i] + Cc[5] * Jg[1][i] + Cc[2] * Jg[2][i];
       }
-    }
-#ifdef BB_EXP_DUP_CPASS
+    };
+    // a team-summed contact's partials
+    auto partials = [&](const T (&Jg)[3][6], const T (&f)[3], const T (&w)[3][6]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) gg[i] -= Jg[0][i] * f[0] + Jg[1][i] * f[1] + Jg[2][i] * f[2];
+#pragma unroll
+      for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j <= i; j++) Hg[i * (i + 1) / 2 + j] += Jg[0][i] * w[0][j] + Jg[1][i] * w[1][j] + Jg[2][i] * w[2][j];
+    };
+    auto contact_pass = [&]() __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) gg[i] = 0;
+#pragma unroll
+      for (int i = 0; i < 21; i++) Hg[i] = 0;
+      {
+        for (int c = tl; c < ngc; c += L) {
+          const bool wheel = c < 3;
+          T jar[3] = {jar0[0], jar0[1], jar0[2]}, Dc = 0, Jg[3][6];  // c == tl: carried
+          if (!wheel) {
+            T ar[3];
+            ground_get<BODY>(m, W, c - 3, Jg, ar, Dc);
+            if (fresh || c != tl) {
+#pragma unroll
+              for (int r = 0; r < 3; r++) jar[r] = ground_dot(Jg, r, a) - ar[r];
+            }
+          } else if (fresh) {
+#pragma unroll
+            for (int r = 0; r < 3; r++) jar[r] = wheel_dot(W.wc[c], c, r, a) - W.wc[c].aref[r];
+          }
+          if (fresh && c == tl) {
+#pragma unroll
+            for (int r = 0; r < 3; r++) jar0[r] = jar[r];
+          }
+          T f[3], Cc[6];
+          cone_of(wheel, c, jar, Dc, f, Cc);
+          if (wheel) {
+            wheel_put(c, f, Cc);
+          } else {
+            T w[3][6];
+            cj_of(Cc, Jg, w);
+            partials(Jg, f, w);
+          }
+        }
+      }
+    };
+#ifdef BB_EXP_DUP_CPASS  // timing experiment: the wheel / ball-terrain contact pass twice
+    {
+      contact_pass();
+      T z = 0;
+      for (int i = 0; i < 6; i++) z += gg[i];
+      for (int i = 0; i < 21; i++) z += Hg[i];
+      asm volatile("" :: "v"(z) : "memory");
+      team_sync();
     }
 #endif
+    contact_pass();
     // base-tree contacts (full kernel), contact-parallel in world form
     // (BodyFrame): lane tl rebuilds contact b0 + tl's frame and cone force and
     // forms A = F' C F and phi = F' f; each contact's A, phi and its column
@@ -732,10 +774,12 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     T h[NV];
 #pragma unroll
     for (int k = 0; k < NV; k++) h[k] = BB_HROW(k);  // dense M row
-    T Ma = 0;
+    if (fresh) {
+      T Ma = 0;
 #pragma unroll
-    for (int k = 0; k < NV; k++) Ma += h[k] * a[k];
-    const T mq = rowl ? Ma - qfs_i : T(0);
+      for (int k = 0; k < NV; k++) Ma += h[k] * a[k];
+      mq = rowl ? Ma - qfs_i : T(0);
+    }
     T gi = mq;
     static_for<3>([&](auto wc_) {
       constexpr int w = decltype(wc_)::value;
@@ -885,9 +929,10 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     const T sMs = tsum(sown * Ms), gs = tsum(sown * mq);
     // this lane's first contact's term from its jar; later rounds rebuild theirs
     LsTerm<T> lt;
+    T x[3] = {0, 0, 0};  // J s of the lane's first-round contact
     if (tl < ngc) {
       const bool wheel = tl < 3;
-      T x[3], Dc[3];
+      T Dc[3];
       if (wheel) {
         const WheelCon<T>& C = W.wc[tl];
 #pragma unroll
@@ -985,6 +1030,11 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     T sn = 0, an2 = 0;
 #pragma unroll
     for (int i = 0; i < NV; i++) { a[i] += alpha * s[i]; sn += s[i] * s[i]; an2 += a[i] * a[i]; }
+    if constexpr (CARRY) {  // jar and M a follow a along s
+#pragma unroll
+      for (int r = 0; r < 3; r++) jar0[r] += alpha * x[r];
+      mq = rowl ? mq + alpha * Ms : T(0);
+    }
     PH(6)
     if (alpha * alpha * sn <= T(1e-30) + m.step_rel2 * (1 + an2)) { it++; break; }
     // MuJoCo's improvement stop (mj_solPrimal: scale * (oldcost - cost) < tolerance)
