@@ -32,6 +32,20 @@
 #include "bb_solve.h"
 
 namespace bb {
+
+// (compiled by the host check too: tests/hostcheck/overhead_check.cpp)
+// Where lane tl of a team stores entry k (0 .. NV - 2) of its row of L for the transpose through LDS
+// (chol_solve_rows): the strictly lower triangle packed by rows (row i at i (i - 1) / 2); an entry on
+// or right of the diagonal, and all of lane 15's (no row), in the one spare slot behind the
+// triangle, which nobody reads.  Written as a base plus k: the base is what the lanes select, k
+// stays in the store's offset field.
+constexpr int LTR_SPARE = NV * (NV - 1) / 2, LTR_SLOTS = LTR_SPARE + 1;
+BB_HD int ltr_slot(int tl, int k) {
+  const int rw = tl < NV ? tl : 0;
+  const int base = k < rw ? rw * (rw - 1) / 2 : LTR_SPARE - k;
+  return base + k;
+}
+
 #ifdef __HIP_DEVICE_COMPILE__
 namespace t16 {
 
@@ -314,9 +328,10 @@ __device__ __forceinline__ void chol_rows(T (&h)[NV], T hdi, T (&diag)[NV], int 
 //   forward   L y = -g, column sweep: lane j's right-hand side broadcast, every
 //             later row updates its own
 //   backward  L' s = y, column sweep over L' after a transpose through LDS
-//             (scr: >= NV (NV - 1) / 2 elements of team scratch): lane k holds
-//             column k of L, so s_i needs one broadcast instead of a team sum
-template <bool FUSE = false, typename T>
+//             (scr: >= NV (NV - 1) / 2 elements of team scratch; SPARE: one more,
+//             LTR_SLOTS): lane k holds column k of L, so s_i needs one broadcast
+//             instead of a team sum
+template <bool FUSE = false, bool SPARE = false, typename T>
 __device__ __forceinline__ void chol_solve_rows(const T (&h)[NV], const T (&diag)[NV], T gown, T (&s)[NV], T& sown,
                                                 int tl, T* scr) {
   T b = tl < NV ? -gown : T(0);
@@ -333,8 +348,16 @@ __device__ __forceinline__ void chol_solve_rows(const T (&h)[NV], const T (&diag
       b -= h[j] * yj;  // rows <= j no longer read their right-hand side
     }
   });
-  // strictly lower L, packed by rows (row i at i (i - 1) / 2)
-  if (tl < NV) {
+  // strictly lower L, packed by rows (row i at i (i - 1) / 2).  SPARE (a caller whose scratch has
+  // the spare slot; solve16 in the fast kernels with registers to spare): every lane
+  // stores all fourteen columns, without an exec-mask branch round each store: the address is
+  // selected (ltr_slot), an entry that is not below the diagonal goes to the spare slot
+  if constexpr (SPARE) {
+    static_for<NV - 1>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      scr[ltr_slot(tl, k)] = h[k];
+    });
+  } else if (tl < NV) {
     static_for<NV - 1>([&](auto kc) {
       constexpr int k = decltype(kc)::value;
       if (k < tl) scr[tl * (tl - 1) / 2 + k] = h[k];
@@ -784,9 +807,16 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     static_for<3>([&](auto wc_) {
       constexpr int w = decltype(wc_)::value;
       const int p = wheel_pos(row, w);
-      if (p >= 0) {
-        const WheelCon<T>& C = W.wc[w];
-        const T* q = wCf + 9 * w + 6;
+      const WheelCon<T>& C = W.wc[w];
+      const T* q = wCf + 9 * w + 6;
+      if constexpr (FUSE) {
+        // a row without a column in wheel w (the other wheels' hinges) reads column 0 and
+        // subtracts a selected 0: no exec-mask branch round the three loads and FMAs (the same
+        // bits: x - 0 is x, also for x = -0).  In the kernels that take the spare-slot stores
+        const int pc = p >= 0 ? p : 0;
+        const T t = C.J[0][pc] * q[0] + C.J[1][pc] * q[1] + C.J[2][pc] * q[2];
+        gi -= p >= 0 ? t : T(0);
+      } else if (p >= 0) {
         gi -= C.J[0][p] * q[0] + C.J[1][p] * q[1] + C.J[2][p] * q[2];
       }
     });
@@ -901,12 +931,13 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
 #ifdef BB_EXP_DUP_TRSV  // timing experiment: the two triangular sweeps twice
     {
       T s2[NV], so2;
-      chol_solve_rows<FUSE>(h, diag, gi, s2, so2, tl, &W.u.hes.cj[0][0][0]);
+      chol_solve_rows<FUSE, FUSE>(h, diag, gi, s2, so2, tl, &W.u.hes.cj[0][0][0]);
       asm volatile("" :: "v"(s2[0]), "v"(so2) : "memory");
       team_sync();
     }
 #endif
-    chol_solve_rows<FUSE>(h, diag, gi, s, sown, tlx, &W.u.hes.cj[0][0][0]);  // cj is dead after the Hessian
+    static_assert(sizeof(W.u.hes.cj) >= LTR_SLOTS * sizeof(T), "L's transpose and its spare slot do not fit cj");
+    chol_solve_rows<FUSE, FUSE>(h, diag, gi, s, sown, tlx, &W.u.hes.cj[0][0][0]);  // cj is dead after the Hessian
     T d0 = tsum(sown * gi);
     bool fin = true;
 #pragma unroll
