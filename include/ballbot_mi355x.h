@@ -17,6 +17,7 @@
  *   bb_step          ctrl = -clip(10a); mj_step; _get_obs;      ballbot_env.py:903-1036
  *                    reward plugin; termination
  *   bb_render_depth  RGBDInputs depth cams (_get_obs)           sensors/rgbd.py:46-82
+ *   bb_render_view   render() (rgb_array, tracking free camera) ballbot_env.py:1077-1135
  *   bb_ppo_loss      SB3 PPO.train minibatch loss + grads
  *   bb_adamw_clip    SB3 PPO.train clip_grad_norm_ + AdamW step
  *   bb_ppo_mlp_step  SB3 PPO.train minibatch (forward, loss, backward, clip,
@@ -57,7 +58,7 @@
 extern "C" {
 #endif
 
-#define BB_ABI_VERSION 20
+#define BB_ABI_VERSION 21
 #define BB_NQ 17
 #define BB_NV 15
 #define BB_OBS 15
@@ -150,6 +151,27 @@ int bb_gae(const float* rewards_dev, const float* values_dev, const uint8_t* epi
  * Enqueued on stream, after bb_step / bb_reset. */
 int bb_render_depth(bb_handle* h, float* depth_dev, float* rel_ts_dev, int height, int width, int every,
                     int force, void* stream);
+/* World-view RGB frames (ABI 21): render(), ballbot_env.py:1077-1135.  View v shows env
+ * env_ids_dev[v] (int32 on the device; any order, duplicates allowed; an id outside [0, n) gives a
+ * background-only image) from MuJoCo's free camera: lookat = the base body's origin +
+ * lookat_offset, forward f = (cos e cos a, cos e sin a, sin e), up u = (-sin e cos a, -sin e sin a,
+ * cos e), right = f x u, origin = lookat - distance f; pixel (i, j), row 0 on top, looks along
+ * right xc + up yc + f with xc = (2 (j + 1/2) / W - 1) (W / H) tan(fovy / 2), yc = (1 - 2 (i + 1/2)
+ * / H) tan(fovy / 2).  The image is this project's own definition, not
+ * MuJoCo's OpenGL image: the depth cameras' surfaces, flat base colours, one shading rule.
+ * rgb_dev uint8[n_views][height][width][3]; ids_dev int8[n_views][height][width] (may be NULL)
+ * receives the surface per pixel: 0 none, 1 ground, 2 ball, 3 tower, 4-5 sticks, 6-8 wheels.
+ * Two launches on stream, no sync and no host read.  The scratch of n_views scenes lives in the
+ * handle and grows at the first call with that many views: growth is an allocation, so a graph
+ * capture must follow a first call of that size. */
+typedef struct {
+  int height, width;
+  float fovy_deg, azimuth_deg, elevation_deg, distance;
+  float lookat_offset[3];
+} bb_view_cfg;
+void bb_default_view(bb_view_cfg* c); /* 640, 480, 45, 90, -20, 2.5, (0, 0, 0.2) */
+int bb_render_view(bb_handle* h, const int32_t* env_ids_dev, int n_views, const bb_view_cfg* cfg, uint8_t* rgb_dev,
+                   int8_t* ids_dev, void* stream);
 /* PPO update: fused minibatch loss of SB3 PPO.train (diagonal Gaussian,
  * clipped surrogate, MSE value loss, entropy; ppo/ppo.py, called through
  * model.learn at ballbot_rl/training/train.py:284) and its gradients.  All

@@ -92,6 +92,19 @@ class RolloutArgs(C.Structure):
                                          "ep_l_out", "buf_terminal_obs", "buf_flags")]
 
 
+class ViewCfg(C.Structure):
+    """bb_view_cfg (include/ballbot_mi355x.h): frame size and MuJoCo's free camera."""
+    _fields_ = [
+        ("height", C.c_int),
+        ("width", C.c_int),
+        ("fovy_deg", C.c_float),
+        ("azimuth_deg", C.c_float),
+        ("elevation_deg", C.c_float),
+        ("distance", C.c_float),
+        ("lookat_offset", C.c_float * 3),
+    ]
+
+
 ENCODER_FIELDS = ("conv1_w", "conv1_b", "bn1_w", "bn1_b", "bn1_mean", "bn1_var", "bn1_count",
                   "conv2_w", "conv2_b", "bn2_w", "bn2_b", "bn2_mean", "bn2_var", "bn2_count",
                   "fc_w", "fc_b", "bn3_w", "bn3_b", "bn3_mean", "bn3_var", "bn3_count")
@@ -110,16 +123,16 @@ EXPORTS = [
     "bb_ppo_mlp_act", "bb_rollout_track", "bb_depth_encoder_workspace_bytes", "bb_depth_encoder",
     "bb_set_terrain_stream", "bb_get_env_terrain", "bb_kernel_times", "bb_step_multi", "bb_rollout",
     "bb_set_terrain_rng", "bb_get_terrain_rng", "bb_pair_counters", "bb_pair_env_times", "bb_check",
-    "bb_reward_terms",
+    "bb_reward_terms", "bb_default_view", "bb_render_view",
 ]
 
-ABI_VERSION = 20  # include/ballbot_mi355x.h BB_ABI_VERSION
+ABI_VERSION = 21  # include/ballbot_mi355x.h BB_ABI_VERSION
 
 _lib = None
 
 
-HIP_SOURCES = ("bb_kernels.hip", "bb_pair.hip", "bb_terrain.hip", "bb_rollout.hip", "bb_render.hip", "bb_ppo.hip",
-               "bb_mlp.hip", "bb_encoder.hip", "bb_episode_log.hip")
+HIP_SOURCES = ("bb_kernels.hip", "bb_pair.hip", "bb_terrain.hip", "bb_rollout.hip", "bb_render.hip", "bb_view.hip",
+               "bb_ppo.hip", "bb_mlp.hip", "bb_encoder.hip", "bb_episode_log.hip")
 # per-source flags: the relief pair's unit without MachineLICM (bb_kernels.hip: bb_pair_launch_tu)
 SOURCE_FLAGS = {"bb_pair.hip": ["-mllvm", "-disable-machine-licm"]}
 
@@ -215,6 +228,9 @@ def _load(path: Path):
     L.bb_generate_perlin.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(PerlinCfg), C.c_float]
     L.bb_get_hfield.argtypes = [vp, C.c_int, fp]
     L.bb_render_depth.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.bb_default_view.argtypes = [C.POINTER(ViewCfg)]
+    L.bb_default_view.restype = None
+    L.bb_render_view.argtypes = [vp, vp, C.c_int, C.POINTER(ViewCfg), vp, vp, vp]
     L.bb_ppo_loss.argtypes = [vp] * 8 + [C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp]
     L.bb_adamw_clip.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp] + [C.c_double] * 5 + [vp]
     L.bb_gae.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]
@@ -228,7 +244,7 @@ def _load(path: Path):
                                    C.c_float, C.c_float, vp, C.c_int64, vp, C.c_int64, vp]
     L.bb_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.bb_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
-    for name in [n for n in EXPORTS if n not in ("bb_default_params", "bb_abi_version")]:
+    for name in [n for n in EXPORTS if n not in ("bb_default_params", "bb_default_view", "bb_abi_version")]:
         getattr(L, name).restype = C.c_int
     if L.bb_abi_version() != ABI_VERSION:
         raise NativeLibraryError("ABI version mismatch")

@@ -33,8 +33,11 @@ never clears them, :370-372), appends the episode's terrain seed to
 terrain_seed_history (perlin) and, with `cams`, dumps the depth frames rendered
 during the episode's steps.  With every switch off no directory is created.
 
-Not provided: the MuJoCo viewer (GUI) and RGB video rendering (`render()`) --
-outside the hot path.
+`render()` returns the world-view frame uint8 (640, 480, 3) of the tracking free
+camera (reference :1077-1135) from the HIP ray caster (csrc/bb_view.hip); the image
+is this project's own definition, not MuJoCo's OpenGL image.
+
+Not provided: the MuJoCo viewer (GUI) -- outside the hot path.
 """
 from __future__ import annotations
 
@@ -229,6 +232,11 @@ class BBotSimulation:
                                         C.c_void_p(self._book.data_ptr()), env._stream()), "bb_reward_terms")
         t = self._terms.cpu().numpy().reshape(2)
         return np.float32(t[0]), np.float32(t[1])
+
+    def render(self):
+        """The third-person frame of the camera that tracks the robot: np.uint8 (640, 480, 3)
+        (ballbot_env.py:1077-1135; _video_renderer_size unpacked as height, width)."""
+        return self._env.render_view()[0].cpu().numpy()
 
     def close(self):
         if self._env is not None:

@@ -44,6 +44,10 @@ class BallbotVecEnv:
     10^4-seed space, generated on the GPU).  `terrain_draws`: an explicit list
     of terrain seeds that every env walks instead (a replayed draw log).
 
+    `render_mode="rgb_array"` enables render(): env 0's world-view frame as a numpy
+    array (ballbot_env.py:1077-1135).  render_view() renders any envs into a device
+    tensor and needs no render_mode.  Nothing is rendered unless one of them is called.
+
     `log_options` (with env_config's `logging` section on top, ballbot_env.py:214-218)
     turns on the reference's per-episode log files (_save_logs, :673-699): keys
     `reward_terms` (term_1.npy / term_2.npy), `terrain_seeds` (terrain_seed_history),
@@ -55,7 +59,7 @@ class BallbotVecEnv:
     buffer or file is added.
     """
 
-    metadata = {"render_modes": []}
+    metadata = {"render_modes": ["rgb_array"], "render_fps": 30}
     render_mode = None
 
     def __init__(
@@ -80,9 +84,14 @@ class BallbotVecEnv:
         opt_disableflags: int = 0,
         log_options: Optional[Dict[str, Any]] = None,
         first_env: int = 0,
+        render_mode: Optional[str] = None,
     ):
         from .config import params_from_configs
 
+        if render_mode is not None and render_mode not in self.metadata["render_modes"]:
+            raise ValueError(f"Invalid render_mode: {render_mode}. Supported modes: {self.metadata['render_modes']}")
+        if render_mode is not None:  # the class attribute stays None: nothing renders unless asked
+            self.render_mode = render_mode
         self._log_on = False  # the per-episode logs (log_options), set up after the first reset
         if not torch.cuda.is_available():
             raise RuntimeError("BallbotVecEnv needs a ROCm GPU (torch.cuda.is_available() is False)")
@@ -274,6 +283,44 @@ class BallbotVecEnv:
             raise RuntimeError("cameras are disabled (BallbotVecEnv(..., disable_cameras=False))")
         self._render(force)
         return self.depth
+
+    def render_view(self, env_ids=None, height: int = 640, width: int = 480, *, azimuth: float = 90.0,
+                    elevation: float = -20.0, distance: float = 2.5, lookat_offset=(0.0, 0.0, 0.2),
+                    fovy: float = 45.0, out: Optional[torch.Tensor] = None,
+                    ids_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """World-view RGB frames uint8 [k, H, W, 3] of the envs `env_ids` (None: env 0; a sequence or an
+        int32 device tensor, any order, duplicates allowed) at the current state, from MuJoCo's free
+        camera tracking each env's base (bb_render_view; the image is defined in DESIGN.md §5).
+        `out` (uint8 [k, H, W, 3]) and `ids_out` (int8 [k, H, W]: 0 none, 1 ground, 2 ball, 3 tower,
+        4-5 sticks, 6-8 wheels) are contiguous device tensors written in place.  Enqueued on the
+        current stream; the first call with more views than any before allocates scratch."""
+        if env_ids is None:
+            env_ids = [0]
+        if isinstance(env_ids, torch.Tensor):
+            ids = env_ids.to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+        else:
+            ids = torch.as_tensor(np.asarray(env_ids, np.int32).reshape(-1)).to(self.device)
+        k, H, W = int(ids.numel()), int(height), int(width)
+        if H < 1 or W < 1:
+            raise ValueError(f"render_view: frame size {H}x{W} must be at least 1x1")
+        if out is None:
+            out = torch.empty(k, H, W, 3, dtype=torch.uint8, device=self.device)
+        for t, shape, dt, name in ((out, (k, H, W, 3), torch.uint8, "out"), (ids_out, (k, H, W), torch.int8, "ids_out")):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or t.device != self.device
+                                  or not t.is_contiguous()):
+                raise ValueError(f"render_view: {name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
+        cfg = N.ViewCfg(H, W, float(fovy), float(azimuth), float(elevation), float(distance),
+                        (C.c_float * 3)(*[float(x) for x in lookat_offset]))
+        N.check(N.lib().bb_render_view(self._h, _ptr(ids), k, C.byref(cfg), _ptr(out), _ptr(ids_out), self._stream()),
+                "bb_render_view")
+        return out
+
+    def render(self):
+        """gymnasium's render() in rgb_array mode: env 0's world-view frame, uint8 numpy [640, 480, 3]
+        (the reference's _video_renderer_size, ballbot_env.py:1077-1135)."""
+        if self.render_mode != "rgb_array":
+            raise RuntimeError('render() needs BallbotVecEnv(..., render_mode="rgb_array")')
+        return self.render_view()[0].cpu().numpy()
 
     def step(self, actions: torch.Tensor):
         """One env.step for all envs: returns (obs[N,15], reward[N], terminated[N], truncated[N], info)."""

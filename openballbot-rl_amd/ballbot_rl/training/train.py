@@ -14,7 +14,13 @@ seed, evaluation.*, env.*, problem.terrain/reward).  Differences, by design:
   depth cameras are on, as in the reference; `frozen_cnn` names an encoder
   pretrained by ballbot_rl.encoders.pretrain (safetensors) -- the reference's
   pickled encoder files are never loaded -- else the rgbd
-  branches are the Extractor's trainable CNNs.
+  branches are the Extractor's trainable CNNs;
+* the `visualization` section's videos (record_videos, video_freq, video_episodes,
+  async_video_recording; extra keys video_length, video_frame_skip, video_size) are animated
+  PNGs under <out>/videos/, rendered by the HIP world-view renderer on a one-env video env of
+  the recorder's own, by rank 0 only (callbacks.VideoRecorder: the reference records on its
+  eval env).  With no `visualization` section nothing is recorded -- the reference's default
+  config turns the videos on.
 Output directory layout as the reference: outputs/experiments/runs/
 {timestamp}_{algo}_{terrain}_{reward}_seed{seed}/ with config.yaml, info.txt,
 progress.csv (SB3 columns), best_model.safetensors and final_model.safetensors.
@@ -153,11 +159,21 @@ def main(config: Dict[str, Any], seed: int, out: Optional[str] = None, total_tim
     model.warm_up()  # the update graphs and first library calls, before the run (SB3's _setup_model)
     eval_freq = int(eval_cfg.get("freq", 5000))
     on_rollout = None
+    recorder = None
     if rank == 0 and eval_env is not None:
-        from ballbot_rl.training.callbacks import EvalCallback
+        from ballbot_rl.training.callbacks import EvalCallback, EveryNth, VideoRecorder, video_options
 
+        hooks = {}
+        vo = video_options(config)
+        if vo is not None:  # a one-env env of the recorder's own: the eval env's terrain streams stay as they are
+            freq = vo.pop("video_freq")
+            recorder = VideoRecorder(make_env(config, 1, dev, seed + 2 * n_total, precision), out_path / "videos", **vo)
+            if freq == "on_new_best":
+                hooks["callback_on_new_best"] = recorder
+            else:
+                hooks["callback_after_eval"] = recorder if freq == "every_eval" else EveryNth(recorder, freq)
         on_rollout = EvalCallback(eval_env, n_eval_episodes=n_eval, eval_freq=eval_freq, n_total_envs=n_total,
-                                  log_path=out_path / "results", best_model_save_path=out_path)
+                                  log_path=out_path / "results", best_model_save_path=out_path, **hooks)
 
     total = int(float(total_timesteps if total_timesteps is not None else config["total_timesteps"]))
     model.learn(total_timesteps=total, rollout_callback=on_rollout)
@@ -166,6 +182,8 @@ def main(config: Dict[str, Any], seed: int, out: Optional[str] = None, total_tim
     env.close()
     if eval_env is not None:
         eval_env.close()
+    if recorder is not None:
+        recorder.close()  # joins the writer thread
     model.out_path = out_path
     return model
 

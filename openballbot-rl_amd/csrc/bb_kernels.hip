@@ -39,6 +39,7 @@
 #include "bb_rollout.h"
 #include "bb_episode_log.h"
 #include "bb_render.h"
+#include "bb_view.h"
 #include "bb_ppo.h"
 #include "bb_mlp.h"
 #include "bb_encoder.h"
@@ -1907,6 +1908,8 @@ struct bb_handle {
   TerrainSrc* tsrc_dev = nullptr;
   CamRig rig;  // depth cameras in the base body (bb_render_depth)
   void* scenes = nullptr;
+  void* view_scenes = nullptr;  // world-view renderer (bb_render_view): one scene per view, grown on demand
+  int view_cap = 0;
   volatile int* fault_host = nullptr;  // Dev.fault's host side (hipHostMalloc, mapped)
 };
 
@@ -2490,6 +2493,7 @@ int bb_destroy(bb_handle* h) {
   (void)hipStreamDestroy(h->side); (void)hipEventDestroy(h->fork); (void)hipEventDestroy(h->join);
   for (hipEvent_t e : h->tev) (void)hipEventDestroy(e);
   (void)hipFree(h->scenes);
+  (void)hipFree(h->view_scenes);
   if (h->fault_host) (void)hipHostFree((void*)h->fault_host);
   delete h;
   return 0;
@@ -2571,6 +2575,50 @@ int bb_render_depth(bb_handle* h, float* depth, float* rel_ts, int height, int w
   if (launch_depth(h->fp64 != 0, h->mf, h->rig, rd, height, width, every, force, double(h->md.h), h->scenes, depth, rel_ts,
                    (hipStream_t)stream))
     return fail("bb_render_depth: launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
+void bb_default_view(bb_view_cfg* c) {
+  memset(c, 0, sizeof *c);
+  c->height = 640;  // the reference unpacks _video_renderer_size = (640, 480) as (height, width)
+  c->width = 480;
+  c->fovy_deg = 45.f;  // MuJoCo's global fovy (the XML sets none)
+  c->azimuth_deg = 90.f;
+  c->elevation_deg = -20.f;
+  c->distance = 2.5f;  // |(0, -2, 1.5)|
+  c->lookat_offset[0] = 0.f; c->lookat_offset[1] = 0.f; c->lookat_offset[2] = 0.2f;
+}
+
+int bb_render_view(bb_handle* h, const int32_t* env_ids, int n_views, const bb_view_cfg* c, uint8_t* rgb, int8_t* ids,
+                   void* stream) {
+  if (!h || !c || !rgb) return fail("bb_render_view: NULL argument");
+  if (c->height < 1 || c->width < 1) return fail("bb_render_view: image size %dx%d must be >= 1x1", c->height, c->width);
+  if (n_views < 0) return fail("bb_render_view: n_views must be >= 0 (got %d)", n_views);
+  if (n_views == 0) return 0;
+  if (!env_ids) return fail("bb_render_view: NULL env_ids");
+  if (!(c->fovy_deg > 0.f && c->fovy_deg < 180.f)) return fail("bb_render_view: fovy %g out of range (0,180)", c->fovy_deg);
+  HIPCHK(hipSetDevice(h->device));
+  if (n_views > h->view_cap) {  // an allocation: a graph capture must follow a first call of this size
+    (void)hipFree(h->view_scenes);
+    h->view_scenes = nullptr;
+    h->view_cap = 0;
+    HIPCHK(hipMalloc(&h->view_scenes, view_scene_bytes(n_views)));
+    h->view_cap = n_views;
+  }
+  // MuJoCo's free camera: forward from azimuth / elevation, origin = lookat - distance * forward
+  const double rad = 3.14159265358979323846 / 180.0, a = c->azimuth_deg * rad, e = c->elevation_deg * rad;
+  const double f[3] = {cos(e) * cos(a), cos(e) * sin(a), sin(e)}, u[3] = {-sin(e) * cos(a), -sin(e) * sin(a), cos(e)};
+  const double r[3] = {f[1] * u[2] - f[2] * u[1], f[2] * u[0] - f[0] * u[2], f[0] * u[1] - f[1] * u[0]};
+  ViewCam cam;
+  for (int i = 0; i < 3; i++) {
+    cam.R[3 * i + 0] = float(r[i]); cam.R[3 * i + 1] = float(u[i]); cam.R[3 * i + 2] = float(-f[i]);
+    cam.rel[i] = double(c->lookat_offset[i]) - double(c->distance) * f[i];
+  }
+  cam.tan_half = float(tan(0.5 * c->fovy_deg * rad));
+  RenderDev rd{h->n, h->d.qpos, h->d.steps, h->d.terrain, h->bank, h->size_z, h->hmax};
+  if (launch_view(h->fp64 != 0, h->mf, rd, cam, env_ids, n_views, c->height, c->width, h->view_scenes, rgb, ids,
+                  (hipStream_t)stream))
+    return fail("bb_render_view: launch failed: %s", hipGetErrorString(hipGetLastError()));
   return 0;
 }
 
