@@ -210,6 +210,64 @@ BB_HD T wheel_dot(const WheelCon<T>& C, int w, int r, const T* x) {
   return acc;
 }
 
+// Device code: nothing is scheduled across this point.  One wave per SIMD hides no latency, and
+// with the register file full the compiler sinks each LDS read to its use, so a chain of
+// products waits out one read's latency per pair of operands; the fence keeps a batch of reads
+// issued together above the arithmetic that consumes them.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BB_ISSUE_FENCE() __builtin_amdgcn_sched_barrier(0)
+#else
+#define BB_ISSUE_FENCE() ((void)0)
+#endif
+
+// J x for the three rows of wheel contact w at once: each row is wheel_dot's chain (J[r][6]
+// x_hinge, then columns 0..5, then 7..12: the same bits), the 39 entries of J and the three of
+// e (the contact's aref or D, handed back unchanged) are read in two batches ahead of the
+// products, and the rows' independent chains are interleaved, so that the second batch's
+// latency is covered by the first one's arithmetic.
+template <typename T>
+BB_HD void wheel_dot3(const WheelCon<T>& C, int w, const T* x, T (&o)[3], const T (&e)[3], T (&eo)[3]) {
+  const T xh = hinge_sel(w, x);
+  T ja[3][7], jb[3][6];
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int i = 0; i < 7; i++) ja[r][i] = C.J[r][i];
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) jb[r][i] = C.J[r][7 + i];
+    eo[r] = e[r];
+  }
+  BB_ISSUE_FENCE();
+#pragma unroll
+  for (int r = 0; r < 3; r++) o[r] = ja[r][6] * xh;
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int r = 0; r < 3; r++) o[r] += ja[r][i] * x[i];
+  BB_ISSUE_FENCE();
+#pragma unroll
+  for (int i = 0; i < 6; i++)
+#pragma unroll
+    for (int r = 0; r < 3; r++) o[r] += jb[r][i] * x[9 + i];
+}
+
+template <typename T>
+BB_HD void wheel_dot3(const WheelCon<T>& C, int w, const T* x, T (&o)[3]) {
+  T e[3];
+  wheel_dot3(C, w, x, o, C.aref, e);
+}
+
+// jar = J x - aref of wheel contact w: the three rows batched
+template <typename T>
+BB_HD void wheel_jar3(const WheelCon<T>& C, int w, const T* x, T (&jar)[3]) {
+  T ar[3];
+  wheel_dot3(C, w, x, jar, C.aref, ar);
+#pragma unroll
+  for (int r = 0; r < 3; r++) jar[r] -= ar[r];
+}
+
 // J_r x over the ball dofs for ground-contact rows J (ground_rows)
 template <typename T>
 BB_HD T ground_dot(const T (&J)[3][6], int r, const T* x) {

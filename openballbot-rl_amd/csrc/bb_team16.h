@@ -519,6 +519,25 @@ constexpr bool kCarry = true;
 constexpr bool kCarry = false;
 #endif
 
+// -DBB_NO_LDS_BATCH_LS / _CP / _HESS (A/B builds): the FUSE kernels' line-search setup, first
+// contact pass and Hessian row read the wheel Jacobian at each use, as the other kernels do,
+// instead of in batches ahead of the arithmetic (wheel_dot3, BB_ISSUE_FENCE: bb_solve.h).
+#ifndef BB_NO_LDS_BATCH_LS
+constexpr bool kLdsBatchLs = true;
+#else
+constexpr bool kLdsBatchLs = false;
+#endif
+#ifndef BB_NO_LDS_BATCH_CP
+constexpr bool kLdsBatchCp = true;
+#else
+constexpr bool kLdsBatchCp = false;
+#endif
+#ifndef BB_NO_LDS_BATCH_HESS
+constexpr bool kLdsBatchHess = true;
+#else
+constexpr bool kLdsBatchHess = false;
+#endif
+
 template <bool BODY, bool FUSE = false, typename T>
 __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, int tl) {
   if constexpr (!BODY) nb = 0;
@@ -630,8 +649,12 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
               for (int r = 0; r < 3; r++) jar[r] = ground_dot(Jg, r, a) - ar[r];
             }
           } else if (fresh) {
+            if constexpr (FUSE && kLdsBatchCp) {
+              wheel_jar3(W.wc[c], c, a, jar);  // the three rows' reads batched: the same bits
+            } else {
 #pragma unroll
-            for (int r = 0; r < 3; r++) jar[r] = wheel_dot(W.wc[c], c, r, a) - W.wc[c].aref[r];
+              for (int r = 0; r < 3; r++) jar[r] = wheel_dot(W.wc[c], c, r, a) - W.wc[c].aref[r];
+            }
           }
           if (fresh && c == tl) {
 #pragma unroll
@@ -854,6 +877,33 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     // the fp32 solve (Hessians conditioned ~1e10, DESIGN fp32) is held to a count of outliers that
     // moves with the order.
     auto wheel_blocks = [&](T (&hh)[NV]) {
+      if constexpr (sizeof(T) == 8 && FUSE && kFmacDpp && kLdsBatchHess) {
+        // the fused form with the reads of all three wheels (own column and packed C: 27 values)
+        // issued ahead of the first cw; wheel by wheel each group of reads was issued behind the
+        // previous wheel's 39 FMAs, three exposed latencies in a row.  Same operands, same order
+        T jc[3][3], Cw[3][6];
+        static_for<3>([&](auto wc_) {
+          constexpr int w = decltype(wc_)::value;
+          const int p = wheel_pos(row, w);
+          const int pc = p >= 0 ? p : 0;
+#pragma unroll
+          for (int r = 0; r < 3; r++) jc[w][r] = W.wc[w].J[r][pc];
+#pragma unroll
+          for (int k = 0; k < 6; k++) Cw[w][k] = wCf[9 * w + k];
+        });
+        BB_ISSUE_FENCE();
+        static_for<3>([&](auto wc_) {
+          constexpr int w = decltype(wc_)::value;
+          const int p = wheel_pos(row, w);
+          const T j0 = p >= 0 ? jc[w][0] : T(0), j1 = p >= 0 ? jc[w][1] : T(0), j2 = p >= 0 ? jc[w][2] : T(0);
+          T u0, u1, u2;
+          cw(Cw[w], j0, j1, j2, u0, u1, u2);
+          fmac_bcast_cols<0, 1, 2, 3, 4, 5, 6 + w, 9, 10, 11, 12, 13, 14>(hh, j0, u0);
+          fmac_bcast_cols<0, 1, 2, 3, 4, 5, 6 + w, 9, 10, 11, 12, 13, 14>(hh, j1, u1);
+          fmac_bcast_cols<0, 1, 2, 3, 4, 5, 6 + w, 9, 10, 11, 12, 13, 14>(hh, j2, u2);
+        });
+        return;
+      }
       static_for<3>([&](auto wc_) {
         constexpr int w = decltype(wc_)::value;
         const int p = wheel_pos(row, w);
@@ -966,8 +1016,14 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
       T Dc[3];
       if (wheel) {
         const WheelCon<T>& C = W.wc[tl];
+        if constexpr (FUSE && kLdsBatchLs) {
+          // J s with the reads of J and D in two batches ahead of the three rows' interleaved
+          // chains, not waited for pair by pair (19 exposed LDS latencies per iteration before)
+          wheel_dot3(C, tl, s, x, C.D, Dc);
+        } else {
 #pragma unroll
-        for (int r = 0; r < 3; r++) { x[r] = wheel_dot(C, tl, r, s); Dc[r] = C.D[r]; }
+          for (int r = 0; r < 3; r++) { x[r] = wheel_dot(C, tl, r, s); Dc[r] = C.D[r]; }
+        }
       } else {
         T Jg[3][6], ar[3], D;
         ground_get<BODY>(m, W, tl - 3, Jg, ar, D);

@@ -3,7 +3,9 @@
 Counts the instructions of each kernel's solve16 between the `; PHASE_MARK k`
 comments that a -DBB_ISA_MARKS build leaves in the assembly (bb_solve.h: PH).
 Static counts: a loop body counts once, so the line-search loop (phase 9) is
-one evaluation and the contact loops one round.
+one evaluation and the contact loops one round.  The last column, read-wait,
+counts the waits on a just-issued LDS read: an `s_waitcnt lgkmcnt(0)` within
+three instructions after a `ds_read*`.
 
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DBB_ISA_MARKS -I openballbot-rl_amd/csrc \
       --cuda-device-only -S -o /tmp/bbk.s openballbot-rl_amd/csrc/bb_kernels.hip
@@ -38,10 +40,11 @@ def classify(op):
 def main(path):
     func, marks, counts = None, [], {}
     cur = None
+    since_read = None  # instructions since the last ds_read*, None when there was none in this phase
     for line in open(path):
         m = re.match(r"^(_Z[^:\s]+):", line)
         if m:
-            func, cur = m.group(1), None
+            func, cur, since_read = m.group(1), None, None
             continue
         m = re.search(r"; PHASE_MARK (\d+)", line)
         if m and func:
@@ -50,12 +53,21 @@ def main(path):
                 cur = None
                 continue
             counts.setdefault(func, {}).setdefault(cur, Counter())
+            since_read = None
             continue
         s = line.strip()
         if cur is None or not s or s.startswith((";", ".")) or s.endswith(":"):
             continue
         op = s.split()[0]
         counts[func][cur][classify(op)] += 1
+        # a wait for everything outstanding within three instructions of an LDS read's issue: the
+        # read's whole latency is exposed (one wave per SIMD has nothing else to run)
+        if op.startswith("ds_read"):
+            since_read = 0
+        elif since_read is not None:
+            since_read += 1
+            if op == "s_waitcnt" and "lgkmcnt(0)" in s and since_read <= 3:
+                counts[func][cur]["rwait"] += 1
     for func, ph in counts.items():
         print(func[:90])
         tot = Counter()
@@ -67,10 +79,10 @@ def main(path):
             nxt = {10: "contact pass", 0: "ground sums", 1: "gradient", 2: "hessian row", 3: "cholesky", 4: "sweeps",
                    5: "ls setup", 8: "ls loop", 9: "update", 6: "conv test"}[k]
             tot.update(c)
-            print("  after mark %d (%-14s) valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d" %
-                  (k, nxt, c["valu"], c["dpp"], c["lds"], c["vmem"], c["salu"], c["wait"]))
-        print("  total                        valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d" %
-              (tot["valu"], tot["dpp"], tot["lds"], tot["vmem"], tot["salu"], tot["wait"]))
+            print("  after mark %d (%-14s) valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d read-wait %3d" %
+                  (k, nxt, c["valu"], c["dpp"], c["lds"], c["vmem"], c["salu"], c["wait"], c["rwait"]))
+        print("  total                        valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d read-wait %3d" %
+              (tot["valu"], tot["dpp"], tot["lds"], tot["vmem"], tot["salu"], tot["wait"], tot["rwait"]))
 
 
 if __name__ == "__main__":
