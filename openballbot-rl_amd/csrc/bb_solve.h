@@ -22,6 +22,8 @@ namespace bb {
 static long g_ls_evals = 0;
 static long g_ls_hist[16] = {0};  // line-search evaluations per Newton iteration
 static long g_alpha1 = 0;         // Newton iterations whose first evaluation (alpha = 1) was accepted
+static long g_ls_snaps = 0;       // trial points shortened to a kink
+static long g_ls_fallbacks = 0;   // searches that ended unconverged
 static int g_stage_iters[4] = {0, 0, 0, 0};  // Newton iterations of each RK stage of the last step
 #endif
 
@@ -344,6 +346,24 @@ struct LsTerm {
       if (ak > 0 && N < mu * Tn && mu * N + Tn > 0) kink = ak;
     }
   }
+  // prep without branches (the FUSE kernels): the kink's division runs on a guarded denominator
+  // and the result is selected, the same bits as prep's for every input.  With x, D, mu, f1 and
+  // f2 all zero (an idle lane) the term is inert: eval and cost add exact zeros, kink = -1
+  BB_HD void prep_sel(const T* j0, const T* x, T mu_, T f1, T f2, const T* D, T Dm_) {
+    mu = mu_;
+    Dm = Dm_;
+    u0[0] = mu * j0[0]; u0[1] = f1 * j0[1]; u0[2] = f2 * j0[2];
+    du[0] = mu * x[0]; du[1] = f1 * x[1]; du[2] = f2 * x[2];
+    b0 = D[0] * j0[0] * x[0] + D[1] * j0[1] * x[1] + D[2] * j0[2] * x[2];
+    b1 = D[0] * x[0] * x[0] + D[1] * x[1] * x[1] + D[2] * x[2] * x[2];
+    c0 = T(0.5) * (D[0] * j0[0] * j0[0] + D[1] * j0[1] * j0[1] + D[2] * j0[2] * j0[2]);
+    vv = du[1] * du[1] + du[2] * du[2];
+    const bool pos = vv > 0;
+    const T ak = -(u0[1] * du[1] + u0[2] * du[2]) / (pos ? vv : T(1));
+    const T N = u0[0] + ak * du[0], U1 = u0[1] + ak * du[1], U2 = u0[2] + ak * du[2];
+    const T Tn = sqrt(U1 * U1 + U2 * U2);
+    kink = (pos & (ak > 0) & (N < mu * Tn) & (mu * N + Tn > 0)) ? ak : T(-1);
+  }
   BB_HD void none() {
     u0[0] = u0[1] = u0[2] = du[0] = du[1] = du[2] = T(0);
     u0[0] = T(1);  // separated: top zone at every alpha
@@ -436,7 +456,63 @@ struct LineSearch {
   // an unconverged search falls back to the last point with phi' < 0 (a
   // guaranteed decrease for convex phi)
   BB_HD T fallback() const { return lo > 0 ? lo : (hi > 0 ? hi * dlo / (dlo - dhi) : T(0)); }
+  // crosses without short-circuit evaluation: the same truth value for every input (NaNs included)
+  BB_HD bool crosses_sel(T k) const {
+    const bool up = alpha > prev;
+    const bool between = up ? ((k > prev) & (k < alpha)) : ((k < prev) & (k > alpha));
+    return between & (k > lo) & ((hi < 0) | (k < hi));
+  }
 };
+
+// One evaluation of the line search without branches, in two parts.  ls_exits forms d1 and dmag
+// from the team sums s1 and sm of the terms' phi' and magnitude bound at l.alpha, as the
+// branching loop does, and folds that loop's three exits into `done` (tolerance or roundoff:
+// ls_ok as well; a NaN phi': done only).  ls_next moves the state on to the next trial point from
+// (d1, d2), snapped to the nearest crossed kink: kmin(n, up) is the minimum over the team's terms
+// of (n.crosses_sel(kink) ? (up ? kink : -kink) : 1e30) for the updated state n.  A search that
+// is done, before this evaluation or by it, keeps alpha, its bracket and ls_ok, so the teams of
+// a wave may leave the loop at different evaluations or run on together: alpha, ls_ok, the
+// fallback and the bits of every trial point are those of the loop with the three breaks.  The
+// FUSE kernels (bb_team16.h) leave the loop between the two parts once every search of the wave
+// is done; ls_advance is both in a row (the host check's form).
+// the exits: d1 = phi'(l.alpha) is handed back for ls_next
+template <typename T>
+BB_HD T ls_exits(const LineSearch<T>& l, bool& ls_ok, bool& done, T s1, T sm, T gs, T sMs, T d0, T ls_tol) {
+  const T alpha = l.alpha;
+  const T d1 = gs + alpha * sMs + s1;
+  const T dmag = fabs(gs) + fabs(alpha * sMs) + sm;
+  const bool conv = (fabs(d1) <= ls_tol * fabs(d0)) | (fabs(d1) <= T(32) * eps_of<T>() * dmag);
+  ls_ok = ls_ok | (!done & conv);
+  done = done | conv | !(d1 == d1);
+  return d1;
+}
+// the next trial point from (d1, d2), for a search that is not done
+template <typename T, typename KinkMin>
+BB_HD void ls_next(LineSearch<T>& l, bool done, T d1, T d2, KinkMin&& kmin) {
+  LineSearch<T> n = l;
+  n.update(d1, d2);
+  const bool up = n.alpha > n.prev;
+  const T big = T(1e30);
+  const T kv = kmin(n, up);
+  const T ks = up ? kv : -kv;
+  n.dx = kv < big ? fabs(ks - n.prev) : n.dx;
+  n.alpha = kv < big ? ks : n.alpha;
+  // what outlives the search is alpha and the bracket (fallback): those are held once done; the
+  // rest of the state only steers later trials, which a finished search no longer has
+  l.lo = done ? l.lo : n.lo;
+  l.dlo = done ? l.dlo : n.dlo;
+  l.hi = done ? l.hi : n.hi;
+  l.dhi = done ? l.dhi : n.dhi;
+  l.alpha = done ? l.alpha : n.alpha;
+  l.flo = n.flo; l.fhi = n.fhi; l.prev = n.prev; l.dx = n.dx; l.dxold = n.dxold;
+  l.side = n.side; l.same = n.same;
+}
+template <typename T, typename KinkMin>
+BB_HD void ls_advance(LineSearch<T>& l, bool& ls_ok, bool& done, T s1, T s2, T sm, T gs, T sMs, T d0, T ls_tol,
+                      KinkMin&& kmin) {
+  const T d1 = ls_exits(l, ls_ok, done, s1, sm, gs, sMs, d0, ls_tol);
+  ls_next(l, done, d1, sMs + s2, kmin);
+}
 
 // What solve_team carries across its Newton iterations, as mj_solPrimal does:
 // every contact's jar = J a - aref and M a.  Computed from the warm start once
@@ -675,10 +751,16 @@ BB_HD int solve_team(const ModelT<T>& m, EnvWork<T>& W, const T* qfs, int ng, T*
         T kn = T(-1);
         for (int c = 0; c < nc; c++)
           if (lsr.crosses(lst[c].kink) && (kn < 0 || (up ? lst[c].kink < kn : lst[c].kink > kn))) kn = lst[c].kink;
+#ifdef BB_SOLVE_STATS
+        if (kn > 0) g_ls_snaps++;
+#endif
         if (kn > 0) lsr.snap(kn);
       }
 #endif
     }
+#ifdef BB_SOLVE_STATS
+    if (!ls_ok) g_ls_fallbacks++;
+#endif
     if (!ls_ok) lsr.alpha = lsr.fallback();
 #ifdef BB_SOLVE_TRACE
     printf("   d0 %.3e alpha %.3e ls_ok %d lo %.3e hi %.3e dlo %.3e dhi %.3e\n", double(d0), double(alpha), int(ls_ok),

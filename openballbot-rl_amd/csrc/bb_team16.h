@@ -538,6 +538,37 @@ constexpr bool kLdsBatchHess = true;
 constexpr bool kLdsBatchHess = false;
 #endif
 
+// -DBB_NO_TAIL_UNIFORM / _LS_SELECT / _PREP_SELECT (A/B builds): the FUSE kernels' Newton loop
+// with fewer exec-mask branches.  The teams of a wave leave the line search at different
+// evaluations, so every lane-dependent `if` there is walked with masks; these forms compute on
+// guarded operands and select, or add the same exact zeros, with the parent's operands,
+// operation order and summation order: the same bits.
+//   kTailUniform  the contact pass takes its first round (c = tl) as straight-line code, where
+//                 `fresh` alone decides what the loop decided per contact, and its later rounds
+//                 (c >= 16: more than 13 ball-terrain contacts) under a ballot read as a scalar
+//   kLsSelect     one line-search evaluation is ls_exits + ls_next (bb_solve.h): the three sums
+//                 interleaved, the three exits folded into one `done`, the loop left by a scalar
+//                 branch once every search of the wave has ended, no region round the next trial
+//   kPrepSelect   the line-search setup forms an idle lane's inert term from zeroed operands and
+//                 the kink by a select (LsTerm::prep_sel)
+// The three are kept together: measured alone on the MI355X each is level with the parent or
+// slower, together 1.1% faster; the register allocation decides as much as the branches.
+#ifndef BB_NO_TAIL_UNIFORM
+constexpr bool kTailUniform = true;
+#else
+constexpr bool kTailUniform = false;
+#endif
+#ifndef BB_NO_LS_SELECT
+constexpr bool kLsSelect = true;
+#else
+constexpr bool kLsSelect = false;
+#endif
+#ifndef BB_NO_PREP_SELECT
+constexpr bool kPrepSelect = true;
+#else
+constexpr bool kPrepSelect = false;
+#endif
+
 template <bool BODY, bool FUSE = false, typename T>
 __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, int tl) {
   if constexpr (!BODY) nb = 0;
@@ -583,6 +614,9 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
   // at the 512-register limit, spills with the loop-carried values (step_kernel<double, true>:
   // 16 -> 548 B of scratch, also with them parked in LDS across the line search); it recomputes.
   constexpr bool CARRY = kCarry && !BODY;
+  constexpr bool UTAIL = FUSE && !BODY && kTailUniform;
+  constexpr bool LSSEL = FUSE && !BODY && kLsSelect;
+  constexpr bool PREPSEL = FUSE && !BODY && kPrepSelect;
   T jar0[3] = {0, 0, 0}, mq = 0;
   int it = 0;
   bool held = false;  // the improvement stop was overridden once (IMPR_GRAD, bb_physics.h)
@@ -595,6 +629,13 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     int tlx = tl;
     asm volatile("" : "+v"(tlx));
     const bool fresh = !CARRY || it == 0;  // jar and M a from a
+    // does any team still iterating in this wave hold contacts past its sixteen lanes?  A
+    // ballot read as a scalar.  Round the later rounds of the line search and of the cost sum the
+    // compiler drops the test (the loops' own condition implies it, and a taken s_cbranch_execz
+    // already skips them); it stands round the contact pass's
+    bool more = true;
+    if constexpr (UTAIL) more = __ballot(nc > L) != 0;
+    (void)more;
     // ---- (1) contact pass, contact-parallel (c = tl, tl + 16, ...): the
     // wheels' cone force f and Hessian C (3x3, packed) into LDS for the row
     // owners; ball-terrain contacts add ball-block gradient and C-weighted J'J
@@ -637,7 +678,55 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
       for (int i = 0; i < 6; i++) gg[i] = 0;
 #pragma unroll
       for (int i = 0; i < 21; i++) Hg[i] = 0;
-      {
+      if constexpr (UTAIL) {
+        // first round: c == tl, so the carried jar is this contact's and `fresh` alone decides
+        if (tl < ngc) {
+          const int c = tl;
+          const bool wheel = c < 3;
+          T jar[3] = {jar0[0], jar0[1], jar0[2]}, Dc = 0, Jg[3][6];
+          if (!wheel) {
+            T ar[3];
+            ground_get<BODY>(m, W, c - 3, Jg, ar, Dc);
+            if (fresh) {
+#pragma unroll
+              for (int r = 0; r < 3; r++) jar[r] = ground_dot(Jg, r, a) - ar[r];
+            }
+          } else if (fresh) {
+            if constexpr (kLdsBatchCp) {
+              wheel_jar3(W.wc[c], c, a, jar);
+            } else {
+#pragma unroll
+              for (int r = 0; r < 3; r++) jar[r] = wheel_dot(W.wc[c], c, r, a) - W.wc[c].aref[r];
+            }
+          }
+          if (fresh) {
+#pragma unroll
+            for (int r = 0; r < 3; r++) jar0[r] = jar[r];
+          }
+          T f[3], Cc[6];
+          cone_of(wheel, c, jar, Dc, f, Cc);
+          if (wheel) {
+            wheel_put(c, f, Cc);
+          } else {
+            T w[3][6];
+            cj_of(Cc, Jg, w);
+            partials(Jg, f, w);
+          }
+        }
+        // later rounds: ball-terrain contacts only (c >= 16), jar rebuilt from a
+        if (more) {
+          for (int c = tl + L; c < ngc; c += L) {
+            T jar[3], Dc = 0, Jg[3][6], ar[3];
+            ground_get<BODY>(m, W, c - 3, Jg, ar, Dc);
+#pragma unroll
+            for (int r = 0; r < 3; r++) jar[r] = ground_dot(Jg, r, a) - ar[r];
+            T f[3], Cc[6], w[3][6];
+            cone_of(false, c, jar, Dc, f, Cc);
+            cj_of(Cc, Jg, w);
+            partials(Jg, f, w);
+          }
+        }
+      } else {
         for (int c = tl; c < ngc; c += L) {
           const bool wheel = c < 3;
           T jar[3] = {jar0[0], jar0[1], jar0[2]}, Dc = 0, Jg[3][6];  // c == tl: carried
@@ -1011,7 +1100,31 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     // this lane's first contact's term from its jar; later rounds rebuild theirs
     LsTerm<T> lt;
     T x[3] = {0, 0, 0};  // J s of the lane's first-round contact
-    if (tl < ngc) {
+    if constexpr (PREPSEL) {
+      // one path: an idle lane (tl >= ngc = nc) keeps x = 0 and takes D = mu = f1 = f2 = 0 and a
+      // zero jar, which prep_sel turns into an inert term (what LsTerm::none gives it otherwise:
+      // the same exact zeros into the sums, no kink)
+      const bool act = tl < ngc, wheel = tl < 3;
+      T Dc[3] = {0, 0, 0};
+      if (wheel) {
+        const WheelCon<T>& C = W.wc[tl];
+        if constexpr (kLdsBatchLs) {
+          wheel_dot3(C, tl, s, x, C.D, Dc);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 3; r++) { x[r] = wheel_dot(C, tl, r, s); Dc[r] = C.D[r]; }
+        }
+      } else if (act) {
+        T Jg[3][6], ar[3], D;
+        ground_get<BODY>(m, W, tl - 3, Jg, ar, D);
+#pragma unroll
+        for (int r = 0; r < 3; r++) { x[r] = ground_dot(Jg, r, s); Dc[r] = D; }
+      }
+      const T one = act ? T(1) : T(0);
+      const T mu = wheel ? muw : one, f1 = wheel ? muw : one, f2 = wheel ? m.fr_wheel[1] : one;
+      const T j0[3] = {act ? jar0[0] : T(0), act ? jar0[1] : T(0), act ? jar0[2] : T(0)};
+      lt.prep_sel(j0, x, mu, f1, f2, Dc, Dc[0] * (wheel ? kdw : T(0.5)));
+    } else if (tl < ngc) {
       const bool wheel = tl < 3;
       T Dc[3];
       if (wheel) {
@@ -1075,14 +1188,39 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
 #else
     lsr.init(d0);
     PH(8)
+    if constexpr (LSSEL) {
+      // one evaluation without branches (ls_advance): the team's search ends through `done`
+      bool done = false;
+      for (int ls = 1; ls <= m.ls_maxiter && !done; ls++) {
+        const T alpha = lsr.alpha;
+        T p[3] = {0, 0, 0};  // phi', phi'', magnitude bound
+        lt.eval(alpha, p[0], p[1], p[2]);
+        if (more) {
+          for (int c = tl + L; c < nc; c += L) {
+            LsTerm<T> lc;
+            ls_term<BODY>(m, W, c, ng, nc, a, s, kdw, lc);
+            lc.eval(alpha, p[0], p[1], p[2]);
+          }
+        }
+        tsum_n(p);  // tsum's bits for each, the three DPP chains interleaved
+        const T d1 = ls_exits(lsr, ls_ok, done, p[0], p[2], gs, sMs, d0, m.ls_tol);
+        // every search of the wave has ended: no next trial point to form (a scalar branch)
+        if (__ballot(!done) == 0) break;
+        ls_next(lsr, done, d1, sMs + p[1], [&](const LineSearch<T>& n, bool up) {
+          return tmin(n.crosses_sel(lt.kink) ? (up ? lt.kink : -lt.kink) : T(1e30));
+        });
+      }
+    } else {
     for (int ls = 1; ls <= m.ls_maxiter; ls++) {
       const T alpha = lsr.alpha;
       T d1p = 0, d2p = 0, dmp = 0;
       lt.eval(alpha, d1p, d2p, dmp);
-      for (int c = tl + L; c < nc; c += L) {
-        LsTerm<T> lc;
-        ls_term<BODY>(m, W, c, ng, nc, a, s, kdw, lc);
-        lc.eval(alpha, d1p, d2p, dmp);
+      if (more) {  // always, unless the later rounds sit behind the wave-uniform test
+        for (int c = tl + L; c < nc; c += L) {
+          LsTerm<T> lc;
+          ls_term<BODY>(m, W, c, ng, nc, a, s, kdw, lc);
+          lc.eval(alpha, d1p, d2p, dmp);
+        }
       }
       // phi' decides most evaluations: the magnitude bound (roundoff test) and
       // phi'' (the next trial) are summed only when it does not
@@ -1100,6 +1238,7 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
       lsr.dx = kv < big ? fabs(ks - lsr.prev) : lsr.dx;
       lsr.alpha = kv < big ? ks : lsr.alpha;
     }
+    }
 #endif
     if (!ls_ok) lsr.alpha = lsr.fallback();
     PH(9)
@@ -1108,10 +1247,12 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     // the cost change of the step (MuJoCo's improvement test below), closed form on
     // the line: alpha s'(Ma - qfs) + alpha^2 s'Ms / 2 + sum_c phi_c(alpha) - phi_c(0)
     T dc = lt.cost(alpha) - lt.cost(T(0));
-    for (int c = tl + L; c < nc; c += L) {  // contacts past the team's lanes (full kernel only)
-      LsTerm<T> lc;
-      ls_term<BODY>(m, W, c, ng, nc, a, s, kdw, lc);
-      dc += lc.cost(alpha) - lc.cost(T(0));
+    if (more) {
+      for (int c = tl + L; c < nc; c += L) {  // contacts past the team's lanes
+        LsTerm<T> lc;
+        ls_term<BODY>(m, W, c, ng, nc, a, s, kdw, lc);
+        dc += lc.cost(alpha) - lc.cost(T(0));
+      }
     }
     const T dcost = alpha * (gs + T(0.5) * alpha * sMs) + tsum(dc);
     T sn = 0, an2 = 0;

@@ -5,7 +5,10 @@ comments that a -DBB_ISA_MARKS build leaves in the assembly (bb_solve.h: PH).
 Static counts: a loop body counts once, so the line-search loop (phase 9) is
 one evaluation and the contact loops one round.  The last column, read-wait,
 counts the waits on a just-issued LDS read: an `s_waitcnt lgkmcnt(0)` within
-three instructions after a `ds_read*`.
+three instructions after a `ds_read*`.  Two more columns count the exec-mask
+control flow: xbr, the `s_cbranch_exec*` instructions, and short, the bodies of
+at most 45 instructions that an `s_cbranch_execz` skips forward over (the code
+between the branch and its target), attributed to the branch's phase.
 
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DBB_ISA_MARKS -I openballbot-rl_amd/csrc \
       --cuda-device-only -S -o /tmp/bbk.s openballbot-rl_amd/csrc/bb_kernels.hip
@@ -40,11 +43,13 @@ def classify(op):
 def main(path):
     func, marks, counts = None, [], {}
     cur = None
+    nins, labels, execz = {}, {}, {}  # per function: instructions so far, label -> index, (phase, index, target)
     since_read = None  # instructions since the last ds_read*, None when there was none in this phase
     for line in open(path):
         m = re.match(r"^(_Z[^:\s]+):", line)
         if m:
             func, cur, since_read = m.group(1), None, None
+            nins[func], labels[func], execz[func] = 0, {}, []
             continue
         m = re.search(r"; PHASE_MARK (\d+)", line)
         if m and func:
@@ -56,10 +61,19 @@ def main(path):
             since_read = None
             continue
         s = line.strip()
+        m = re.match(r"^(\.L[\w$.]+):", s)
+        if m and func:
+            labels[func][m.group(1)] = nins[func]
+        if func and s and not s.startswith((";", ".")) and not s.endswith(":"):
+            nins[func] += 1
         if cur is None or not s or s.startswith((";", ".")) or s.endswith(":"):
             continue
         op = s.split()[0]
         counts[func][cur][classify(op)] += 1
+        if op.startswith("s_cbranch_exec"):
+            counts[func][cur]["xbr"] += 1
+            if op == "s_cbranch_execz":
+                execz[func].append((cur, nins[func], s.split()[1]))
         # a wait for everything outstanding within three instructions of an LDS read's issue: the
         # read's whole latency is exposed (one wave per SIMD has nothing else to run)
         if op.startswith("ds_read"):
@@ -68,6 +82,13 @@ def main(path):
             since_read += 1
             if op == "s_waitcnt" and "lgkmcnt(0)" in s and since_read <= 3:
                 counts[func][cur]["rwait"] += 1
+    bodies = {}
+    for func, brs in execz.items():
+        for ph_, idx, target in brs:
+            n = labels[func].get(target, -1) - idx  # instructions between the branch and its target
+            if 0 <= n <= 45:
+                counts[func][ph_]["short"] += 1
+                bodies.setdefault(func, {}).setdefault(ph_, []).append(n)
     for func, ph in counts.items():
         print(func[:90])
         tot = Counter()
@@ -79,10 +100,11 @@ def main(path):
             nxt = {10: "contact pass", 0: "ground sums", 1: "gradient", 2: "hessian row", 3: "cholesky", 4: "sweeps",
                    5: "ls setup", 8: "ls loop", 9: "update", 6: "conv test"}[k]
             tot.update(c)
-            print("  after mark %d (%-14s) valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d read-wait %3d" %
-                  (k, nxt, c["valu"], c["dpp"], c["lds"], c["vmem"], c["salu"], c["wait"], c["rwait"]))
-        print("  total                        valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d read-wait %3d" %
-              (tot["valu"], tot["dpp"], tot["lds"], tot["vmem"], tot["salu"], tot["wait"], tot["rwait"]))
+            print("  after mark %d (%-14s) valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d read-wait %3d xbr %3d short %3d %s" %
+                  (k, nxt, c["valu"], c["dpp"], c["lds"], c["vmem"], c["salu"], c["wait"], c["rwait"], c["xbr"], c["short"],
+                   sorted(bodies.get(func, {}).get(k, []))))
+        print("  total                        valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d read-wait %3d xbr %3d short %3d" %
+              (tot["valu"], tot["dpp"], tot["lds"], tot["vmem"], tot["salu"], tot["wait"], tot["rwait"], tot["xbr"], tot["short"]))
 
 
 if __name__ == "__main__":
