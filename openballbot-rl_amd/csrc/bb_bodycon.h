@@ -395,12 +395,15 @@ BB_HD bool cylinder_prism(const Seg<T>& g, const PrismG<T>& P, T& dist, T* n, T*
   bool sep = false;
   // both signs of an axis from one set of dot products (see capsule_prism):
   // cyl_support(-a) = -a.c + hh |a.u| + r sqrt(1 - (a.u)^2)
-  auto test = [&](const T* ax) {
+  // own: ax is the cylinder's own axis, whose radial term is exactly 0.  Computed, it is the
+  // square root of 1 - (a.a)^2, a rounding residue of either sign: up to 2e-8, times r a few 1e-9
+  // in dist, and another value wherever a.a rounds differently (a fused multiply-add, the oracle)
+  auto test = [&](const T* ax, bool own = false) {
     T mx, mn;
     prism_extent(P, ax, mx, mn);
     const T na = dot3(ax, g.a);
     const T rad = T(1) - na * na;
-    const T sr = sqrt(rad > 0 ? rad : T(0));
+    const T sr = own ? T(0) : sqrt(rad > 0 ? rad : T(0));
     const T ac = dot3(ax, g.c);
     const T csm = -ac + g.hh * fabs(na) + g.r * sr, csp = ac + g.hh * fabs(na) + g.r * sr;  // cyl_support(-a), (a)
     const T dp = mx + csm, dm = -mn + csp;
@@ -416,7 +419,7 @@ BB_HD bool cylinder_prism(const Seg<T>& g, const PrismG<T>& P, T& dist, T* n, T*
   if (sep) return false;
 #pragma unroll
   for (int f = 1; f < 5; f++) test(P.pn[f]);
-  test(g.a);
+  test(g.a, true);
   if (sep) return false;
 #pragma unroll
   for (int k = 0; k < 4; k++) {

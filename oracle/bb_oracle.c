@@ -830,10 +830,12 @@ static int capsule_prism(const Convex* g, const Prism* P, double* dist, double* 
   return 1;
 }
 
-static double cyl_support(const Convex* g, const double* n) {
+/* own: n is (plus or minus) the cylinder's own axis, whose radial term is exactly 0; computed, it
+ * is the square root of 1 - (a.a)^2, a rounding residue of up to 2e-8 (times r a few 1e-9 in dist) */
+static double cyl_support(const Convex* g, const double* n, int own) {
   double na = v3dot(n, g->a);
   double rad = 1 - na * na;
-  return v3dot(n, g->c) + g->hh * fabs(na) + g->r * sqrt(rad > 0 ? rad : 0);
+  return v3dot(n, g->c) + g->hh * fabs(na) + (own ? 0.0 : g->r * sqrt(rad > 0 ? rad : 0));
 }
 
 /* cylinder vs prism; normal from prism to cylinder */
@@ -859,7 +861,7 @@ static int cylinder_prism(const Convex* g, const Prism* P, double* dist, double*
     for (int sgn = -1; sgn <= 1; sgn += 2) {
       double ax[3], mx[3]; v3scl(ax, axes[k], sgn);
       v3scl(mx, ax, -1);
-      double d = prism_support(P, ax) + cyl_support(g, mx); /* = max_P ax.y - min_C ax.x */
+      double d = prism_support(P, ax) + cyl_support(g, mx, k == 5); /* = max_P ax.y - min_C ax.x; axes[5] = g->a */
       if (d <= 0) return 0; /* separating axis */
       if (d < bestd) { bestd = d; v3copy(bn, ax); }
     }

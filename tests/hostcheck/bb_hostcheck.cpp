@@ -194,6 +194,27 @@ int hc_capsule_apart_check(int n, unsigned seed, double* worst) {
   return mism;
 }
 
+// kinematics + collide_ground<T> (bb_physics.h), the serial form of the ball x heightfield pass:
+// out_g[MAXG * NGF] gets the stored (normal, dist) per slot, out_c the ball geom centre it used.
+// Returns the contact count; *overflow is 1 when more than MAXG prisms were hit.
+int hc_collide_ground(const double* qpos, const float* hf, double size_z, int fp64, double* out_g, int* overflow,
+                      double* out_c) {
+  auto run = [&](auto tag) {
+    using T = decltype(tag);
+    const ModelT<T> m = model_for<T>(fp64);
+    T q[NQ], g[MAXG * NGF];
+    for (int i = 0; i < NQ; i++) q[i] = T(qpos[i]);
+    Kin<T> k;
+    kinematics(m, q, k);
+    *overflow = 0;
+    const int ng = collide_ground(m, k, (const T*)nullptr, hf, T(size_z), GStore<T>{g, 1}, overflow);
+    for (int i = 0; i < ng * NGF; i++) out_g[i] = double(g[i]);
+    for (int i = 0; i < 3; i++) out_c[i] = double(k.c[i]);
+    return ng;
+  };
+  return fp64 ? run(double(0)) : run(float(0));
+}
+
 int hc_forward(const double* q, const double* v, const double* ctrl, double* acc, const float* hf, double size_z,
                int fp64, double* extra) {
   return fp64 ? fwd<double>(q, v, ctrl, acc, hf, size_z, 1, extra) : fwd<float>(q, v, ctrl, acc, hf, size_z, 0, extra);

@@ -56,6 +56,7 @@ def lib():
         L.hc_body_jacobian_check.restype = C.c_double
         L.hc_capsule_apart_check.argtypes = [C.c_int, C.c_uint, dp]
         L.hc_pair_kind_of.argtypes = [C.c_int, C.c_int, C.c_int, ip]
+        L.hc_collide_ground.argtypes = [dp, fp, C.c_double, C.c_int, dp, ip, dp]
         _lib = L
     return _lib
 
@@ -73,6 +74,17 @@ def pair_kind_of(b, nf, ns):
     wg = C.c_int(0)
     k = lib().hc_pair_kind_of(int(b), int(nf), int(ns), C.byref(wg))
     return k, wg.value
+
+
+def collide_ground(qpos, hf, size_z=2.0, fp64=True):
+    """kinematics + collide_ground<T>: (g[ng, 4] = normal and dist per slot, overflow, ball centre)."""
+    q = np.ascontiguousarray(qpos, np.float64)
+    hfa = np.ascontiguousarray(hf, np.float32)
+    g = np.zeros(50 * 4)
+    c = np.zeros(3)
+    ov = C.c_int(0)
+    ng = lib().hc_collide_ground(_d(q), _f(hfa), size_z, int(fp64), _d(g), C.byref(ov), _d(c))
+    return g.reshape(50, 4)[:ng].copy(), ov.value, c
 
 
 def model():

@@ -193,6 +193,24 @@ def test_forward_parity_base_tree_contacts(oracle, precision, terrain):
     env.close()
 
 
+def _toppled_states(oracle, n, terrain, rng):
+    """Robots lying on the terrain ("flat" or "hills"), the ball beside them in the air."""
+    qs, vs = [], []
+    for i in range(n):
+        q, v, _ = oracle.reset_state(0.01)
+        t, yaw = np.radians(rng.uniform(80, 100)), rng.uniform(0, 2 * np.pi)
+        ax = np.array([np.cos(yaw), np.sin(yaw), 0.0])
+        q[3:7] = [np.cos(t / 2), *(np.sin(t / 2) * ax)]
+        q[0:2] = rng.uniform(-0.5, 0.5, 2)
+        q[2] = rng.uniform(0.09, 0.12) + (0.0 if terrain == "flat" else 0.02)
+        q[10:13] = [q[0] + 0.6 * np.cos(yaw), q[1] + 0.6 * np.sin(yaw), 0.5]
+        q[13:17] = [1, 0, 0, 0]
+        v[:] = rng.normal(0, 0.1, 15)
+        qs.append(q)
+        vs.append(v)
+    return np.array(qs), np.array(vs)
+
+
 @pytest.mark.parametrize("terrain", ["flat", "hills"])
 def test_forward_parity_contacts_past_lds(oracle, terrain):
     """Toppled robots lying on the terrain: more base-tree contacts than the
@@ -209,20 +227,7 @@ def test_forward_parity_contacts_past_lds(oracle, terrain):
         hf = generate_hills_terrain(293, seed=7).astype(np.float32)
         tcfg = {"type": "hills", "config": {"seed": 7}}
     rng = np.random.default_rng(21)
-    qs, vs = [], []
-    for i in range(n):
-        q, v, _ = oracle.reset_state(0.01)
-        t, yaw = np.radians(rng.uniform(80, 100)), rng.uniform(0, 2 * np.pi)
-        ax = np.array([np.cos(yaw), np.sin(yaw), 0.0])
-        q[3:7] = [np.cos(t / 2), *(np.sin(t / 2) * ax)]
-        q[0:2] = rng.uniform(-0.5, 0.5, 2)
-        q[2] = rng.uniform(0.09, 0.12) + (0.0 if terrain == "flat" else 0.02)
-        q[10:13] = [q[0] + 0.6 * np.cos(yaw), q[1] + 0.6 * np.sin(yaw), 0.5]
-        q[13:17] = [1, 0, 0, 0]
-        v[:] = rng.normal(0, 0.1, 15)
-        qs.append(q)
-        vs.append(v)
-    qs, vs = np.array(qs), np.array(vs)
+    qs, vs = _toppled_states(oracle, n, terrain, rng)
     env = _make_env(n, "fp64", tcfg)
     ctrl = rng.uniform(-10, 10, (n, 3))
     env.set_state(qs, vs, np.zeros((n, 15)))
