@@ -17,6 +17,7 @@
  *   bb_step          ctrl = -clip(10a); mj_step; _get_obs;      ballbot_env.py:903-1036
  *                    reward plugin; termination
  *   bb_render_depth  RGBDInputs depth cams (_get_obs)           sensors/rgbd.py:46-82
+ *   bb_render_rgbd   RGBDInputs RGB-D cams (disable_rgb false)  sensors/rgbd.py:46-82
  *   bb_render_view   render() (rgb_array, tracking free camera) ballbot_env.py:1077-1135
  *   bb_ppo_loss      SB3 PPO.train minibatch loss + grads
  *   bb_adamw_clip    SB3 PPO.train clip_grad_norm_ + AdamW step
@@ -58,6 +59,8 @@
 extern "C" {
 #endif
 
+/* 21 still holds with bb_render_rgbd: the addition is purely additive (no existing symbol, struct
+ * or layout changed), so callers detect it by symbol rather than by version. */
 #define BB_ABI_VERSION 21
 #define BB_NQ 17
 #define BB_NV 15
@@ -151,6 +154,17 @@ int bb_gae(const float* rewards_dev, const float* values_dev, const uint8_t* epi
  * Enqueued on stream, after bb_step / bb_reset. */
 int bb_render_depth(bb_handle* h, float* depth_dev, float* rel_ts_dev, int height, int width, int every,
                     int force, void* stream);
+/* RGB-D cameras cam_0/cam_1, the observation for camera.disable_rgb: false (sensors/rgbd.py:46-82,
+ * ballbot_env.py:241-243, 269-279, 821-822): for every env whose step counter is a multiple of
+ * `every` (or all envs when force != 0), render rgbd_dev float[n][2][4][height][width], planes R, G,
+ * B, D.  The ray, the cadence and rel_ts_dev are bb_render_depth's; the D plane is its quantity,
+ * min(t / len, 1).  Colour rays run to zfar (14.142 m) and R, G, B are the world view's definition
+ * of colour (not MuJoCo's OpenGL image), stored as float32(int(255 c + 0.5)) /
+ * 255.  ids_dev int8[n][2][height][width] (may be NULL) receives the surface per pixel: 0 none,
+ * 1 ground, 2 ball, 3 tower, 4-5 sticks, 6-8 wheels; rel_ts_dev may be NULL.  Two launches on
+ * stream; the scene scratch is allocated at the first call, so a graph capture must follow one. */
+int bb_render_rgbd(bb_handle* h, float* rgbd_dev, float* rel_ts_dev, int8_t* ids_dev, int height, int width,
+                   int every, int force, void* stream);
 /* World-view RGB frames (ABI 21): render(), ballbot_env.py:1077-1135.  View v shows env
  * env_ids_dev[v] (int32 on the device; any order, duplicates allowed; an id outside [0, n) gives a
  * background-only image) from MuJoCo's free camera: lookat = the base body's origin +

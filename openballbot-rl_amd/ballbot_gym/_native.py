@@ -123,7 +123,7 @@ EXPORTS = [
     "bb_ppo_mlp_act", "bb_rollout_track", "bb_depth_encoder_workspace_bytes", "bb_depth_encoder",
     "bb_set_terrain_stream", "bb_get_env_terrain", "bb_kernel_times", "bb_step_multi", "bb_rollout",
     "bb_set_terrain_rng", "bb_get_terrain_rng", "bb_pair_counters", "bb_pair_env_times", "bb_check",
-    "bb_reward_terms", "bb_default_view", "bb_render_view",
+    "bb_reward_terms", "bb_default_view", "bb_render_view", "bb_render_rgbd",
 ]
 
 ABI_VERSION = 21  # include/ballbot_mi355x.h BB_ABI_VERSION
@@ -132,7 +132,7 @@ _lib = None
 
 
 HIP_SOURCES = ("bb_kernels.hip", "bb_pair.hip", "bb_terrain.hip", "bb_rollout.hip", "bb_render.hip", "bb_view.hip",
-               "bb_ppo.hip", "bb_mlp.hip", "bb_encoder.hip", "bb_episode_log.hip")
+               "bb_rgbd.hip", "bb_ppo.hip", "bb_mlp.hip", "bb_encoder.hip", "bb_episode_log.hip")
 # per-source flags: the relief pair's unit without MachineLICM (bb_kernels.hip: bb_pair_launch_tu)
 SOURCE_FLAGS = {"bb_pair.hip": ["-mllvm", "-disable-machine-licm"]}
 
@@ -231,6 +231,7 @@ def _load(path: Path):
     L.bb_default_view.argtypes = [C.POINTER(ViewCfg)]
     L.bb_default_view.restype = None
     L.bb_render_view.argtypes = [vp, vp, C.c_int, C.POINTER(ViewCfg), vp, vp, vp]
+    L.bb_render_rgbd.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.bb_ppo_loss.argtypes = [vp] * 8 + [C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp]
     L.bb_adamw_clip.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp] + [C.c_double] * 5 + [vp]
     L.bb_gae.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]

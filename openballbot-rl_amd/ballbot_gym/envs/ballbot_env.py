@@ -72,12 +72,11 @@ class BBotSimulation:
         self.reward_config = reward_config or {"type": "directional", "config": {"target_direction": [0.0, 1.0]}}
         env_config = dict(env_config or {})
         cam = dict(env_config.get("camera", {}) or {})
-        depth = cam.get("disable_rgb", depth_only) if cam else depth_only
-        if not disable_cameras and not depth:
-            raise ValueError("only depth cameras are rendered (depth_only / camera.disable_rgb must be true)")
+        # the camera config if there is one, else depth_only (ballbot_env.py:241-243, 269-279)
+        depth = bool(cam.get("disable_rgb", depth_only) if cam else depth_only)
         cam.setdefault("height", im_shape["h"])
         cam.setdefault("width", im_shape["w"])
-        cam["disable_rgb"] = True
+        cam["disable_rgb"] = depth
         env_config["camera"] = cam
         self._env_config = env_config
         self.max_ep_steps = int((env_config.get("env", {}) or {}).get(
@@ -87,14 +86,14 @@ class BBotSimulation:
         # the `logging` section of env_config overrides log_options (ballbot_env.py:214-218)
         self.log_options = {"cams": False, "reward_terms": False, **(log_options or {}),
                             **(env_config.pop("logging", None) or {})}
-        self.depth_only = True
+        self.depth_only = depth  # False: rgbd_0 / rgbd_1 are (4, H, W), RGB in [0, 1] plus depth
         self.render_mode = render_mode if render_mode is not None else "rgb_array"
         self.viewer_title = viewer_title
         self.passive_viewer = None
         self.log_dir = None
         self.action_space = spaces.action_space()
-        self.observation_space = spaces.observation_space({"h": cam["height"], "w": cam["width"]}, 1,
-                                                          self.disable_cameras)
+        self.observation_space = spaces.observation_space({"h": cam["height"], "w": cam["width"]},
+                                                          1 if depth else 4, self.disable_cameras)
         self.eval_env = bool(eval_env[0])
         self.step_counter = 0
         self.num_episodes = -1
@@ -203,8 +202,12 @@ class BBotSimulation:
         fl = int(info["done_flags"][0].item())
         o = self._obs()
         if self._log_cams and float(o["relative_image_timestamp"][0]) == 0.0:  # a fresh render (ballbot_env.py:750-758)
-            self.rgbd_hist_0.append(o["rgbd_0"].copy())
-            self.rgbd_hist_1.append(o["rgbd_1"].copy())
+            if self.depth_only:
+                self.rgbd_hist_0.append(o["rgbd_0"].copy())
+                self.rgbd_hist_1.append(o["rgbd_1"].copy())
+            else:  # the reference appends the [H, W, 4] frame, before its transpose
+                self.rgbd_hist_0.append(np.ascontiguousarray(o["rgbd_0"].transpose(1, 2, 0)))
+                self.rgbd_hist_1.append(np.ascontiguousarray(o["rgbd_1"].transpose(1, 2, 0)))
         if self._log_terms:
             t1, t2 = self._reward_terms()
             self.reward_term_1_hist.append(t1)

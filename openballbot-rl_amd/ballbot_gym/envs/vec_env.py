@@ -44,6 +44,12 @@ class BallbotVecEnv:
     10^4-seed space, generated on the GPU).  `terrain_draws`: an explicit list
     of terrain seeds that every env walks instead (a replayed draw log).
 
+    `disable_cameras=False` adds the onboard cameras' keys (rgbd_0, rgbd_1,
+    relative_image_timestamp), rendered every `cam_every` steps and at a reset: depth
+    frames (1, H, W) by default, RGB-D frames (4, H, W) -- R, G, B in [0, 1] plus depth --
+    with env_config["camera"]["disable_rgb"] = False (`cam_channels` 4, `rgbd`
+    f32[N, 2, 4, H, W], `depth` a view of its D planes; the colour is defined in DESIGN.md §5).
+
     `render_mode="rgb_array"` enables render(): env 0's world-view frame as a numpy
     array (ballbot_env.py:1077-1135).  render_view() renders any envs into a device
     tensor and needs no render_mode.  Nothing is rendered unless one of them is called.
@@ -108,8 +114,8 @@ class BallbotVecEnv:
         self.cam_h, self.cam_w = int(cam.get("height", 64)), int(cam.get("width", 64))
         fr = float(cam.get("frame_rate", 90))
         self.cam_every = int(np.ceil((1.0 / fr) / float(opt_timestep or 0.002)))  # effective_camera_frame_rate (ballbot_env.py:389-411)
-        if self.cameras and not cam.get("disable_rgb", True):
-            raise ValueError("only depth cameras are rendered (camera.disable_rgb must be true)")
+        # camera.disable_rgb false: rgbd_0 / rgbd_1 are (4, H, W), RGB in [0, 1] plus depth (bb_render_rgbd)
+        self.cam_channels = 4 if self.cameras and not cam.get("disable_rgb", True) else 1
         self.terrain_config = terrain_config or {"type": "flat", "config": {}}
         self.reward_config = reward_config or {"type": "directional", "config": {"target_direction": [0.0, 1.0]}}
         p, self.reward_obj, self._host_reward = params_from_configs(self.reward_config, env_config, max_ep_steps,
@@ -149,13 +155,20 @@ class BallbotVecEnv:
         self.done = torch.zeros(n, dtype=torch.uint8, device=dev)
         self.pos2d = torch.zeros(n, 2, dtype=torch.float32, device=dev)
         if self.cameras:
-            self.depth = torch.ones(n, 2, self.cam_h, self.cam_w, dtype=torch.float32, device=dev)
+            if self.cam_channels == 4:
+                if "bb_render_rgbd" not in N.EXPORTS:
+                    raise RuntimeError("this build has no bb_render_rgbd (camera.disable_rgb: false)")
+                self.rgbd = torch.ones(n, 2, 4, self.cam_h, self.cam_w, dtype=torch.float32, device=dev)
+                self.depth = self.rgbd[:, :, 3]  # a view: the D plane, for the depth image's readers
+            else:
+                self.depth = torch.ones(n, 2, self.cam_h, self.cam_w, dtype=torch.float32, device=dev)
             self.rel_ts = torch.zeros(n, dtype=torch.float32, device=dev)
         from .. import spaces
 
         # SB3 VecEnv / gymnasium attributes (ballbot_env.py:235-256)
         self.action_space = spaces.action_space()
-        self.observation_space = spaces.observation_space({"h": self.cam_h, "w": self.cam_w}, 1, not self.cameras)
+        self.observation_space = spaces.observation_space({"h": self.cam_h, "w": self.cam_w}, self.cam_channels,
+                                                          not self.cameras)
         self._pending_actions: Optional[torch.Tensor] = None
         self.reset()  # the first reset: draw 0 of every env's generator
         self._log_alloc()
@@ -274,15 +287,29 @@ class BallbotVecEnv:
         return self.obs, {}
 
     def _render(self, force: bool) -> None:
+        if self.cam_channels == 4:  # the D plane comes with the colour: the depth kernel is not launched as well
+            N.check(N.lib().bb_render_rgbd(self._h, _ptr(self.rgbd), _ptr(self.rel_ts), None, self.cam_h, self.cam_w,
+                                           self.cam_every, int(force), self._stream()), "bb_render_rgbd")
+            return
         N.check(N.lib().bb_render_depth(self._h, _ptr(self.depth), _ptr(self.rel_ts), self.cam_h, self.cam_w,
                                         self.cam_every, int(force), self._stream()), "bb_render_depth")
 
     def render_depth(self, force: bool = True) -> torch.Tensor:
-        """Depth images [N, 2, H, W] of cam_0/cam_1 at the current state (linear depth, clipped to 1 m)."""
+        """Depth images [N, 2, H, W] of cam_0/cam_1 at the current state (linear depth, clipped to 1 m).
+        With camera.disable_rgb false this renders the RGB-D frames and returns their D planes (a view)."""
         if not self.cameras:
             raise RuntimeError("cameras are disabled (BallbotVecEnv(..., disable_cameras=False))")
         self._render(force)
         return self.depth
+
+    def render_rgbd(self, force: bool = True) -> torch.Tensor:
+        """RGB-D images [N, 2, 4, H, W] of cam_0/cam_1 at the current state: R, G, B in [0, 1] (the
+        colour defined in DESIGN.md §5) and the linear depth clipped to 1 m."""
+        if not self.cameras or self.cam_channels != 4:
+            raise RuntimeError("RGB-D cameras are off (BallbotVecEnv(..., disable_cameras=False, "
+                               "env_config={'camera': {'disable_rgb': False}}))")
+        self._render(force)
+        return self.rgbd
 
     def render_view(self, env_ids=None, height: int = 640, width: int = 480, *, azimuth: float = 90.0,
                     elevation: float = -20.0, distance: float = 2.5, lookat_offset=(0.0, 0.0, 0.2),
@@ -785,8 +812,11 @@ class BallbotVecEnv:
         o = self.obs if obs is None else obs
         d = {k: o[:, 3 * i:3 * i + 3] for i, k in enumerate(OBS_KEYS)}
         if self.cameras:  # the reference's camera keys (ballbot_env.py:812-826), channels-first
-            d["rgbd_0"] = self.depth[:, 0:1]
-            d["rgbd_1"] = self.depth[:, 1:2]
+            if self.cam_channels == 4:
+                d["rgbd_0"], d["rgbd_1"] = self.rgbd[:, 0], self.rgbd[:, 1]
+            else:
+                d["rgbd_0"] = self.depth[:, 0:1]
+                d["rgbd_1"] = self.depth[:, 1:2]
             d["relative_image_timestamp"] = self.rel_ts.unsqueeze(1)
         return dict(sorted(d.items()))
 

@@ -24,7 +24,8 @@ from ballbot_rl.encoders.models import TinyAutoencoder, save_encoder
 
 @torch.no_grad()
 def collect_depth_images(env, n_frames: int, policy=None, seed: int = 0, max_steps: int = 100000) -> torch.Tensor:
-    """Depth frames [n_frames, 1, H, W] from the env's cameras.
+    """Depth frames [n_frames, 1, H, W] from the env's cameras (of an RGB-D env: the D planes; the
+    autoencoder is depth-only, as the reference's, encoders/models.py:14).
 
     Each step keeps the images of the envs whose cameras rendered in it
     (the reference's 6-step cadence); actions come from `policy.predict`
@@ -45,10 +46,10 @@ def collect_depth_images(env, n_frames: int, policy=None, seed: int = 0, max_ste
             if have >= n_frames:
                 break
         if policy is not None:
-            from ballbot_rl.training.ppo import policy_obs
+            from ballbot_rl.training.ppo import env_images, policy_obs
 
             cams = not policy.features_extractor._proprio_only
-            a = policy.predict(policy_obs(obs, env.depth, env.rel_ts) if cams else obs)
+            a = policy.predict(policy_obs(obs, env_images(env), env.rel_ts) if cams else obs)
         else:
             a = torch.rand(env.num_envs, 3, generator=g, device=env.device) * 2 - 1
         obs, _, _, _, _ = env.step(a)
@@ -128,7 +129,8 @@ def cli_main() -> None:
 
         sd = load_file(a.policy, device="cuda:0")
         cams = any(k.startswith("features_extractor.extractors.rgbd") for k in sd)
-        policy = ActorCriticPolicy(obs_spaces(cameras=cams)).to("cuda:0")
+        policy = ActorCriticPolicy(obs_spaces(cameras=cams, channels=env.cam_channels, height=env.cam_h,
+                                              width=env.cam_w)).to("cuda:0")
         policy.load_state_dict(sd)
         policy.eval()
     imgs = collect_depth_images(env, a.n_frames, policy=policy, seed=a.seed)

@@ -24,9 +24,9 @@ import torch
 
 
 def _policy_obs(env, obs):
-    from ballbot_rl.training.ppo import policy_obs
+    from ballbot_rl.training.ppo import env_images, policy_obs
 
-    return policy_obs(obs, env.depth, env.rel_ts) if getattr(env, "cameras", False) else obs
+    return policy_obs(obs, env_images(env), env.rel_ts) if getattr(env, "cameras", False) else obs
 
 
 @torch.no_grad()

@@ -69,6 +69,15 @@ class Extractor(nn.Module):
                     total += 20
                 else:  # one copy per camera key, as the reference loads it once per key (mlp_policy.py:51-54)
                     enc = copy.deepcopy(frozen_encoder)
+                    first = next((m for m in enc.modules() if isinstance(m, nn.Conv2d)), None)
+                    if first is not None and int(shape[0]) != first.in_channels:  # mlp_policy.py:60-78
+                        want, C = first.in_channels, int(shape[0])
+                        raise ValueError(
+                            f"Channel mismatch: Encoder expects {want} channels "
+                            f"(trained with {'depth-only' if want == 1 else 'RGB-D'}), "
+                            f"but environment provides {C} channels ({'depth-only' if C == 1 else 'RGB-D'}). "
+                            f"Set camera.disable_rgb={'true' if want == 1 else 'false'} "
+                            f"in your environment config to match the encoder.")
                     ex[key] = enc
                     total += [m for m in enc.modules() if isinstance(m, nn.Linear)][-1].out_features
                     for p in enc.parameters():

@@ -126,13 +126,17 @@ def explained_variance(y_pred: torch.Tensor, y_true: torch.Tensor) -> float:
 
 
 class RolloutBuffer:
-    """[T][N] device buffers of one rollout (SB3 RolloutBuffer, device-resident)."""
+    """[T][N] device buffers of one rollout (SB3 RolloutBuffer, device-resident).
+
+    `image_shape`: the camera frames of one env-step, (2, H, W) for the depth cameras or
+    (2, C, H, W) for RGB-D (C = 4).  The RGB-D frames take 2 x 4 x 64 x 64 x 4 B = 131 KB per
+    env-step at 64x64, i.e. 2.7 GB at the reference's 10 envs x 2048 steps."""
 
     def __init__(self, T: int, n: int, obs_dim: int, act_dim: int, device, image_shape=None):
         f32 = dict(dtype=torch.float32, device=device)
         self.T, self.n = T, n
         self.obs = torch.zeros(T, n, obs_dim, **f32)
-        # depth cameras (F2): [T][N][2][H][W] images + relative_image_timestamp
+        # cameras (F2): [T][N][2][H][W] depth or [T][N][2][C][H][W] RGB-D images + relative_image_timestamp
         self.depth = torch.zeros(T, n, *image_shape, **f32) if image_shape else None
         self.rel_ts = torch.zeros(T, n, **f32) if image_shape else None
         self.actions = torch.zeros(T, n, act_dim, **f32)
@@ -155,6 +159,22 @@ class RolloutBuffer:
         return d
 
 
+def env_channels(env) -> int:
+    """Channels of the env's camera frames: 4 with camera.disable_rgb false (RGB-D), else 1 (depth)."""
+    return int(getattr(env, "cam_channels", 1))
+
+
+def env_images(env) -> torch.Tensor:
+    """The env's camera frames as the policy reads them: depth [N, 2, H, W], or RGB-D [N, 2, 4, H, W]."""
+    return env.rgbd if env_channels(env) == 4 else env.depth
+
+
+def image_shape(env) -> tuple:
+    """Shape of one env's camera frames in the rollout buffer (env_images without the env axis)."""
+    c = env_channels(env)
+    return (2, env.cam_h, env.cam_w) if c == 1 else (2, c, env.cam_h, env.cam_w)
+
+
 def policy_obs(obs15: torch.Tensor, depth: Optional[torch.Tensor] = None,
                rel_ts: Optional[torch.Tensor] = None):
     """The policy's observation: the packed proprio tensor, or with cameras the
@@ -163,8 +183,11 @@ def policy_obs(obs15: torch.Tensor, depth: Optional[torch.Tensor] = None,
         return obs15
     d = {k: obs15[:, 3 * i:3 * i + 3] for i, k in enumerate(("actions", "angular_vel", "motor_state",
                                                              "orientation", "vel"))}
-    d["rgbd_0"] = depth[:, 0:1]
-    d["rgbd_1"] = depth[:, 1:2]
+    if depth.dim() == 5:  # RGB-D frames [B, 2, C, H, W]: rgbd_c is [B, C, H, W]
+        d["rgbd_0"], d["rgbd_1"] = depth[:, 0], depth[:, 1]
+    else:
+        d["rgbd_0"] = depth[:, 0:1]
+        d["rgbd_1"] = depth[:, 1:2]
     d["relative_image_timestamp"] = rel_ts.reshape(-1, 1)
     return d
 
@@ -262,7 +285,7 @@ class _UpdateGraphs:
                      "log_probs": torch.zeros(n, device=dev), "advantages": torch.zeros(n, device=dev),
                      "returns": torch.zeros(n, device=dev)}
         if ppo.cameras:
-            self.data["depth"] = torch.zeros(n, 2, ppo.env.cam_h, ppo.env.cam_w, device=dev)
+            self.data["depth"] = torch.zeros(n, *image_shape(ppo.env), device=dev)
             self.data["rel_ts"] = torch.zeros(n, device=dev)
         self.perm = torch.zeros(self.nb, B, dtype=torch.int64, device=dev)
         self.perms = torch.zeros(ppo.n_epochs, self.nb, B, dtype=torch.int64, device=dev)
@@ -650,8 +673,9 @@ class BatchedPPO:
         self._dp_adv_hook = None  # tests: called with each data-parallel minibatch's normalised advantages
         torch.manual_seed(int(seed))
         self.cameras = bool(getattr(env, "cameras", False))
-        img = (2, env.cam_h, env.cam_w) if self.cameras else None
-        spaces = obs_spaces(cameras=True, height=env.cam_h, width=env.cam_w) if self.cameras else obs_spaces()
+        img = image_shape(env) if self.cameras else None
+        spaces = (obs_spaces(cameras=True, channels=env_channels(env), height=env.cam_h, width=env.cam_w)
+                  if self.cameras else obs_spaces())
         self.policy = (policy or ActorCriticPolicy(spaces, 3, net_arch, activation_fn,
                                                    frozen_encoder=frozen_encoder)).to(self.device)
         self._sync_params()
@@ -737,7 +761,7 @@ class BatchedPPO:
         encs = (ext.extractors["rgbd_0"], ext.extractors["rgbd_1"])
         for t in range(T):
             b.obs[t].copy_(self._last_obs)
-            b.depth[t].copy_(env.depth)
+            b.depth[t].copy_(env_images(env))
             b.rel_ts[t].copy_(env.rel_ts)
             feats[:, 0:12].copy_(b.obs[t][:, 0:12])
             feats[:, 12].copy_(b.rel_ts[t])
@@ -887,7 +911,7 @@ class BatchedPPO:
             b.obs[t].copy_(self._last_obs)        # env.obs is reused by the next step
             b.starts[t].copy_(self._last_starts)
             if self.cameras:
-                b.depth[t].copy_(env.depth)
+                b.depth[t].copy_(env_images(env))
                 b.rel_ts[t].copy_(env.rel_ts)
                 pobs = policy_obs(b.obs[t], b.depth[t], b.rel_ts[t])
             else:
@@ -915,7 +939,7 @@ class BatchedPPO:
         env, b = self.env, self.buf
         self.num_timesteps += self.n_envs * self.n_steps * self.world
         last_v = self.policy.predict_values(
-            policy_obs(self._last_obs, env.depth, env.rel_ts) if self.cameras else self._last_obs)
+            policy_obs(self._last_obs, env_images(env), env.rel_ts) if self.cameras else self._last_obs)
         b.advantages, b.returns = self.gae_fn(b.rewards, b.values, b.starts, last_v.contiguous(),
                                               self._last_starts.contiguous(), self.gamma, self.gae_lambda)
         # finished episodes in time order (one host sync per rollout)
@@ -1153,7 +1177,7 @@ class BatchedPPO:
         self.policy.eval()
         with torch.no_grad():
             o = torch.zeros(self.n_envs, 15, device=self.device)
-            self.policy.predict_values(policy_obs(o, self.env.depth, self.env.rel_ts) if self.cameras else o)
+            self.policy.predict_values(policy_obs(o, env_images(self.env), self.env.rel_ts) if self.cameras else o)
             # the update's first calls of torch kernels outside the graphs: the minibatch shuffle
             # (a device randperm of the update's rows: a sort) and explained_variance's reductions,
             # on a throwaway generator so that shuffle_gen's stream is untouched

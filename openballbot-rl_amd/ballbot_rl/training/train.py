@@ -11,7 +11,8 @@ seed, evaluation.*, env.*, problem.terrain/reward).  Differences, by design:
 * the interactive overwrite/updates-per-rollout confirmations (train.py:194-266)
   become printed warnings -- a batch job cannot answer them;
 * checkpoints are safetensors (no pickled SB3 zip); with a `camera` section the
-  depth cameras are on, as in the reference; `frozen_cnn` names an encoder
+  cameras are on, as in the reference (depth frames, or RGB-D frames and 4-channel
+  CNN branches with `camera.disable_rgb: false`); `frozen_cnn` names a depth encoder
   pretrained by ballbot_rl.encoders.pretrain (safetensors) -- the reference's
   pickled encoder files are never loaded -- else the rgbd
   branches are the Extractor's trainable CNNs;

@@ -40,6 +40,7 @@
 #include "bb_episode_log.h"
 #include "bb_render.h"
 #include "bb_view.h"
+#include "bb_rgbd.h"
 #include "bb_ppo.h"
 #include "bb_mlp.h"
 #include "bb_encoder.h"
@@ -1910,6 +1911,7 @@ struct bb_handle {
   void* scenes = nullptr;
   void* view_scenes = nullptr;  // world-view renderer (bb_render_view): one scene per view, grown on demand
   int view_cap = 0;
+  void* rgbd_scenes = nullptr;  // RGB-D cameras (bb_render_rgbd): one scene per (env, camera), on first use
   volatile int* fault_host = nullptr;  // Dev.fault's host side (hipHostMalloc, mapped)
 };
 
@@ -2494,6 +2496,7 @@ int bb_destroy(bb_handle* h) {
   for (hipEvent_t e : h->tev) (void)hipEventDestroy(e);
   (void)hipFree(h->scenes);
   (void)hipFree(h->view_scenes);
+  (void)hipFree(h->rgbd_scenes);
   if (h->fault_host) (void)hipHostFree((void*)h->fault_host);
   delete h;
   return 0;
@@ -2575,6 +2578,22 @@ int bb_render_depth(bb_handle* h, float* depth, float* rel_ts, int height, int w
   if (launch_depth(h->fp64 != 0, h->mf, h->rig, rd, height, width, every, force, double(h->md.h), h->scenes, depth, rel_ts,
                    (hipStream_t)stream))
     return fail("bb_render_depth: launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
+int bb_render_rgbd(bb_handle* h, float* rgbd, float* rel_ts, int8_t* ids, int height, int width, int every, int force,
+                   void* stream) {
+  if (!h || !rgbd) return fail("bb_render_rgbd: NULL argument");
+  if (height < 1 || width < 1 || height > 1024 || width > 1024)
+    return fail("bb_render_rgbd: image size %dx%d out of range [1,1024]", height, width);
+  if (every < 1) return fail("bb_render_rgbd: frame interval must be >= 1 step (got %d)", every);
+  HIPCHK(hipSetDevice(h->device));
+  RenderDev rd{h->n, h->d.qpos, h->d.steps, h->d.terrain, h->bank, h->size_z, h->hmax};
+  // an allocation: a graph capture must follow a first call
+  if (!h->rgbd_scenes) HIPCHK(hipMalloc(&h->rgbd_scenes, rgbd_scene_bytes(h->n)));
+  if (launch_rgbd(h->fp64 != 0, h->mf, h->rig, rd, height, width, every, force, double(h->md.h), h->rgbd_scenes, rgbd,
+                  rel_ts, ids, (hipStream_t)stream))
+    return fail("bb_render_rgbd: launch failed: %s", hipGetErrorString(hipGetLastError()));
   return 0;
 }
 
