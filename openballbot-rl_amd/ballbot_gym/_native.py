@@ -11,6 +11,11 @@ from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "_lib" / "libbb_mi355x.so"
+# bb_kernels.hip with the forward's twin forms and once-per-launch model terms compiled out (the serial
+# pre-phase, csrc/bb_physics.h), linked with the product's other objects: the reference build that
+# tests/test_gpu_prephase.py holds the product to, bit for bit
+SERIAL_LIB_PATH = PKG / "_lib" / "libbb_mi355x_serial.so"
+SERIAL_FLAGS = ["-DBB_NO_TWIN_KIN", "-DBB_NO_TWIN_POS", "-DBB_NO_TWIN_BIAS", "-DBB_NO_MODEL_ONCE"]
 CSRC = PKG.parent / "csrc"
 INCLUDE = PKG.parent.parent / "include"
 
@@ -139,12 +144,14 @@ SOURCE_FLAGS = {"bb_pair.hip": ["-mllvm", "-disable-machine-licm"]}
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     """Compile csrc/*.hip (HIP_SOURCES) for gfx950 into _lib/libbb_mi355x.so: one
-    hipcc -c per source, in parallel (objects under _lib/obj), then one link."""
+    hipcc -c per source, in parallel (objects under _lib/obj), then one link.  bb_kernels.hip is
+    compiled a second time with SERIAL_FLAGS and linked into SERIAL_LIB_PATH (tests only)."""
     import subprocess
     from concurrent.futures import ThreadPoolExecutor
 
     srcs = list(CSRC.glob("*.h")) + list(CSRC.glob("*.hip")) + list(INCLUDE.glob("*.h"))
-    if LIB_PATH.exists() and not force and all(LIB_PATH.stat().st_mtime >= s.stat().st_mtime for s in srcs):
+    if (LIB_PATH.exists() and SERIAL_LIB_PATH.exists() and not force
+            and all(min(LIB_PATH.stat().st_mtime, SERIAL_LIB_PATH.stat().st_mtime) >= s.stat().st_mtime for s in srcs)):
         return LIB_PATH
     obj_dir = LIB_PATH.parent / "obj"
     obj_dir.mkdir(parents=True, exist_ok=True)
@@ -153,6 +160,9 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     for f in HIP_SOURCES:
         obj = obj_dir / (f[:-4] + ".o")
         jobs.append((["hipcc", *flags, *SOURCE_FLAGS.get(f, []), "-c", "-o", str(obj), str(CSRC / f)], obj))
+    serial_obj = obj_dir / "serial" / "bb_kernels.o"
+    serial_obj.parent.mkdir(exist_ok=True)
+    jobs.append((["hipcc", *flags, *SERIAL_FLAGS, "-c", "-o", str(serial_obj), str(CSRC / "bb_kernels.hip")], serial_obj))
     if verbose:
         for cmd, _ in jobs:
             print(" ".join(cmd))
@@ -166,12 +176,14 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     for (cmd, _), r in zip(jobs, results):
         if r.returncode != 0:
             raise subprocess.CalledProcessError(r.returncode, cmd, r.stdout, r.stderr + "\n" + " ".join(cmd))
-    tmp = LIB_PATH.with_suffix(".so.tmp")
-    link = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(tmp), *[str(o) for _, o in jobs]]
-    if verbose:
-        print(" ".join(link))
-    subprocess.run(link, check=True)
-    os.replace(tmp, LIB_PATH)
+    objs = [o for _, o in jobs[:-1]]
+    for out, these in ((LIB_PATH, objs), (SERIAL_LIB_PATH, [serial_obj if o.name == "bb_kernels.o" else o for o in objs])):
+        tmp = out.with_suffix(".so.tmp")
+        link = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(tmp), *[str(o) for o in these]]
+        if verbose:
+            print(" ".join(link))
+        subprocess.run(link, check=True)
+        os.replace(tmp, out)
     return LIB_PATH
 
 

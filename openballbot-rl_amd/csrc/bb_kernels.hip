@@ -82,6 +82,24 @@ __device__ __forceinline__ EnvWork<T>& team_work(unsigned char* smem, int team) 
   return *reinterpret_cast<EnvWork<T>*>(smem + size_t(team) * work_stride<T>());
 }
 
+// The model as the stepping kernels stage it in LDS, once per workgroup: with its model-only
+// terms (ModelOnce, bb_physics.h), which the forward then reads instead of recomputing them.
+// The kernels whose fast step is the FUSE instantiation (step_kernel, multi_step_kernel) stage this
+// type: only FUSE code reaches the terms, through once_of() from the model reference.
+// (-DBB_NO_MODEL_ONCE: the model alone.)
+#ifndef BB_NO_MODEL_ONCE
+template <typename T> using ModelStage = ModelDev<T>;
+#else
+template <typename T> struct ModelStage { ModelT<T> m; };
+#endif
+template <typename T>
+__device__ __forceinline__ void stage_model(ModelStage<T>& ms, const ModelT<T>& mg) {
+  ms.m = mg;
+#ifndef BB_NO_MODEL_ONCE
+  model_once(mg, ms.once);
+#endif
+}
+
 // the terrain-draw configuration (Dev.tsrc; one per handle, in device memory)
 struct TerrainSrc {
   const int* tstream;         // [n_streams][tlen] bank slot of draw k (bb_set_terrain_stream); NULL: none
@@ -341,10 +359,10 @@ __global__ __launch_bounds__(64) void step_kernel(ModelT<T> mg, EnvCfg cfg, Dev 
   }
   // model constants staged in LDS once per workgroup: uniform-address LDS
   // reads broadcast, and ~150 uniform doubles no longer overflow the SGPRs
-  __shared__ ModelT<T> ms;
-  if (threadIdx.x == 0) ms = mg;
+  __shared__ ModelStage<T> ms;
+  if (threadIdx.x == 0) stage_model(ms, mg);
   __syncthreads();
-  const ModelT<T>& m = ms;
+  const ModelT<T>& m = ms.m;
   const Team tm{L, int(threadIdx.x) & (L - 1)};
   const int team = threadIdx.x / L;
   if (team >= epw) return;
@@ -608,10 +626,10 @@ __global__ BB_WPE __launch_bounds__(64) void multi_step_kernel(ModelT<T> mg, Env
   extern __shared__ __align__(16) unsigned char smem[];
   const int nwg = int(gridDim.x), b = int(blockIdx.x);
   const int g = (nwg & 7) ? b : (b & 7) * (nwg >> 3) + (b >> 3);  // XCD-aware order, as step_kernel
-  __shared__ ModelT<T> ms;
-  if (threadIdx.x == 0) ms = mg;
+  __shared__ ModelStage<T> ms;
+  if (threadIdx.x == 0) stage_model(ms, mg);
   __syncthreads();
-  const ModelT<T>& m = ms;
+  const ModelT<T>& m = ms.m;
   const Team tm{L, int(threadIdx.x) & (L - 1)};
   const int team = threadIdx.x / L;
   if (team >= epw) return;

@@ -89,6 +89,68 @@ struct ModelT {
   T qpos0[NQ];
 };
 
+// Forward outside the Newton loop (the FUSE kernels' device code, 16-lane teams): the pre-phase runs the
+// same function on the base and then on the ball in every lane.  The twin forms run the function
+// body once, lanes 0-7 of the team on the base's operands and lanes 8-15 on the ball's, and each
+// half writes its own results to the team's workspace; the model-only terms are computed once
+// per launch (ModelOnce) instead of in every forward.  Same operations on the same operands in
+// the same order: the bits do not change.  The host path keeps the serial forms.
+// -DBB_NO_TWIN_KIN / _TWIN_POS / _TWIN_BIAS / -DBB_NO_MODEL_ONCE (A/B builds, tools/build_variant.sh)
+// turn the items off one by one.
+#ifndef BB_NO_TWIN_KIN
+#define BB_TWIN_KIN 1
+#else
+#define BB_TWIN_KIN 0
+#endif
+#ifndef BB_NO_TWIN_POS
+#define BB_TWIN_POS 1
+#else
+#define BB_TWIN_POS 0
+#endif
+#ifndef BB_NO_TWIN_BIAS
+#define BB_TWIN_BIAS 1
+#else
+#define BB_TWIN_BIAS 0
+#endif
+#if !defined(BB_NO_MODEL_ONCE) && defined(__HIP_DEVICE_COMPILE__)
+#define BB_ONCE 1
+#else
+#define BB_ONCE 0
+#endif
+constexpr int TWIN_L = 16;  // the team size the twin forms are written for
+
+// Terms of the forward that depend on the model alone (model_once fills them with the forward's
+// own expressions).  [0] / [1] of bc, bI, bm: the base composite / the ball, the two operand sets
+// of bias_finish's body_force.
+template <typename T>
+struct ModelOnce {
+  T bc[2][3];   // COM: h0 / m0 | (0, 0, dz)
+  T bI[2][6];   // inertia about the COM: from I0O | IB
+  T bm[2];      // mass: m0 | mB
+  T au[3][3];   // anchor x u[w]
+  T dcj[3];     // cw - jpos
+  T mt;         // m0 + 3 mw
+  T sbd;        // mB dz
+  T MBrr[2];    // IB + mB dz^2, IB
+  T kdw;        // 1 / (mu^2 (1 + mu^2)) of the wheel pairs
+  T rr;         // fr_wheel[0] / fr_wheel[1]
+  T dx, dy;     // hfield grid pitches
+};
+// The device kernels stage the model and these terms together (one per workgroup, LDS); device
+// code reaches the terms from the model reference it is handed.
+template <typename T>
+struct ModelDev {
+  ModelT<T> m;
+  ModelOnce<T> once;
+};
+#if BB_ONCE
+template <typename T>
+__device__ __forceinline__ const ModelOnce<T>& once_of(const ModelT<T>& m) {
+  static_assert(offsetof(ModelDev<T>, m) == 0, "the model leads ModelDev");
+  return reinterpret_cast<const ModelDev<T>*>(&m)->once;
+}
+#endif
+
 // ------------------------------------------------------------- helpers
 template <typename T> BB_HD T dot3(const T* a, const T* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 template <typename T> BB_HD void cross3(T* r, const T* a, const T* b) {
@@ -185,6 +247,56 @@ template <typename T> BB_HD T div_ls(T a, T b) {
 #endif
 }
 
+// ---------------------------------------------------- model-only terms
+// The forward's expressions for the terms of ModelOnce: the serial forms evaluate them in place,
+// model_once evaluates them once per launch -- one text, so one set of bits.
+// base composite for bias_finish: COM h0/m0 and the inertia about it, derived from I0O
+template <typename T> BB_HD void once_base_com(const ModelT<T>& m, T* c0, T* Ic) {
+  c0[0] = m.h0[0] / m.m0; c0[1] = m.h0[1] / m.m0; c0[2] = m.h0[2] / m.m0;
+  T cc = dot3(c0, c0);
+  Ic[0] = m.I0O[0] - m.m0 * (cc - c0[0] * c0[0]); Ic[1] = m.I0O[1] - m.m0 * (cc - c0[1] * c0[1]);
+  Ic[2] = m.I0O[2] - m.m0 * (cc - c0[2] * c0[2]); Ic[3] = m.I0O[3] + m.m0 * c0[0] * c0[1];
+  Ic[4] = m.I0O[4] + m.m0 * c0[0] * c0[2]; Ic[5] = m.I0O[5] + m.m0 * c0[1] * c0[2];
+}
+// the ball for bias_finish: geom offset and inertia about it
+template <typename T> BB_HD void once_ball_com(const ModelT<T>& m, T* cB, T* IcB) {
+  cB[0] = 0; cB[1] = 0; cB[2] = m.dz;
+  IcB[0] = m.IB; IcB[1] = m.IB; IcB[2] = m.IB; IcB[3] = 0; IcB[4] = 0; IcB[5] = 0;
+}
+template <typename T> BB_HD void once_au(const ModelT<T>& m, int w, T* au) { cross3(au, m.anchor, m.u[w]); }
+template <typename T> BB_HD void once_dcj(const ModelT<T>& m, T* d) {
+  d[0] = m.cw[0] - m.jpos[0]; d[1] = m.cw[1] - m.jpos[1]; d[2] = m.cw[2] - m.jpos[2];
+}
+template <typename T> BB_HD void once_mass(const ModelT<T>& m, T& mt, T& sbd, T* MBrr) {
+  const T dz = m.dz;
+  mt = m.m0 + 3 * m.mw;
+  sbd = m.mB * dz;
+  MBrr[0] = m.IB + m.mB * dz * dz;
+  MBrr[1] = m.IB;
+}
+template <typename T> BB_HD T once_kdw(const ModelT<T>& m) {
+  const T muw = m.fr_wheel[0];
+  return T(1) / (muw * muw * (1 + muw * muw));
+}
+template <typename T> BB_HD T once_rr(const ModelT<T>& m) { return m.fr_wheel[0] / m.fr_wheel[1]; }
+template <typename T> BB_HD void once_pitch(const ModelT<T>& m, T& dx, T& dy) {
+  const T sx = m.hf_sx, sy = m.hf_sy;
+  const int N1 = HF_N - 1;
+  dx = 2 * sx / N1; dy = 2 * sy / N1;
+}
+template <typename T> BB_HD void model_once(const ModelT<T>& m, ModelOnce<T>& o) {
+  once_base_com(m, o.bc[0], o.bI[0]);
+  once_ball_com(m, o.bc[1], o.bI[1]);
+  o.bm[0] = m.m0; o.bm[1] = m.mB;
+#pragma unroll
+  for (int w = 0; w < 3; w++) once_au(m, w, o.au[w]);
+  once_dcj(m, o.dcj);
+  once_mass(m, o.mt, o.sbd, o.MBrr);
+  o.kdw = once_kdw(m);
+  o.rr = once_rr(m);
+  once_pitch(m, o.dx, o.dy);
+}
+
 // quaternion (w,x,y,z)
 template <typename T> BB_HD void qmul(T* r, const T* a, const T* b) {
   T w = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
@@ -226,6 +338,24 @@ template <typename T> BB_HD void integrate_pos(T* q, const T* v, T h) {
   q[10] += h * v[9]; q[11] += h * v[10]; q[12] += h * v[11];
   quat_integrate(q + 13, v + 12, h);
 }
+// integrate_pos without its two quaternions (the twin form integrates those one per team half)
+template <typename T> BB_HD void integrate_pos_lin(T* q, const T* v, T h) {
+  q[0] += h * v[0]; q[1] += h * v[1]; q[2] += h * v[2];
+  q[7] += h * v[6]; q[8] += h * v[7]; q[9] += h * v[8];
+  q[10] += h * v[9]; q[11] += h * v[10]; q[12] += h * v[11];
+}
+// where a team half's body sits in qpos / qvel: the base (hi = false) or the ball
+BB_HD constexpr int half_qpos(bool hi) { return hi ? 10 : 0; }
+BB_HD constexpr int half_quat(bool hi) { return hi ? 13 : 3; }
+BB_HD constexpr int half_vlin(bool hi) { return hi ? 9 : 0; }
+BB_HD constexpr int half_vang(bool hi) { return hi ? 12 : 3; }
+// integrate_pos's quaternion step of one half: qo = that body's quaternion after the step
+// (qs = q + half_quat(hi)) from its angular velocity (ws = v + half_vang(hi))
+template <typename T> BB_HD void integrate_quat_half(const T* qs, const T* ws, T h, T* qo) {
+  qo[0] = qs[0]; qo[1] = qs[1]; qo[2] = qs[2]; qo[3] = qs[3];
+  const T w[3] = {ws[0], ws[1], ws[2]};
+  quat_integrate(qo, w, h);
+}
 
 // packed lower-triangular index
 constexpr BB_HD int hidx(int i, int j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
@@ -255,9 +385,31 @@ BB_HD void kinematics_base(const ModelT<T>& m, const T* q, Kin<T>& k) {
   k.c[2] = k.pB[2] + k.RB[8] * m.dz;
 }
 
+// kinematics_base for one half of a team: the base's frame (hi = false) or the ball's with its
+// geom centre; the operands are selected by value (q may be a register array).  qn: the half's
+// normalised quaternion.
+template <typename T>
+BB_HD void kinematics_half(const ModelT<T>& m, const T* q, bool hi, Kin<T>& k, T* qn) {
+  qn[0] = hi ? q[13] : q[3]; qn[1] = hi ? q[14] : q[4]; qn[2] = hi ? q[15] : q[5]; qn[3] = hi ? q[16] : q[6];
+  qnormalize(qn);
+  T R[9];
+  q2mat(R, qn);
+  const T p[3] = {hi ? q[10] : q[0], hi ? q[11] : q[1], hi ? q[12] : q[2]};
+  T* Rk = hi ? k.RB : k.Rb;
+  T* pk = hi ? k.pB : k.pb;
+#pragma unroll
+  for (int i = 0; i < 9; i++) Rk[i] = R[i];
+  pk[0] = p[0]; pk[1] = p[1]; pk[2] = p[2];
+  if (hi) {
+    k.c[0] = p[0] + R[2] * m.dz;
+    k.c[1] = p[1] + R[5] * m.dz;
+    k.c[2] = p[2] + R[8] * m.dz;
+  }
+}
+
 // wheel w's local frame and COM (the device forward runs one wheel per lane)
 template <typename T>
-BB_HD void kinematics_wheel(const ModelT<T>& m, const T* q, int w, Kin<T>& k) {
+BB_HD void kinematics_wheel(const ModelT<T>& m, const T* q, int w, Kin<T>& k, const ModelOnce<T>* mo = nullptr) {
   // xquat_wheel = xquat_base * body_quat * axisangle(axis, theta - theta0)
   T th = q[7 + w] - m.qpos0[7 + w];
   T s = sin(th * T(0.5)), cth = cos(th * T(0.5));
@@ -267,7 +419,9 @@ BB_HD void kinematics_wheel(const ModelT<T>& m, const T* q, int w, Kin<T>& k) {
   qnormalize(qw);
   q2mat(k.Rw[w], qw);
   // origin = anchor - Rw jpos ; COM = origin + Rw cw
-  T d[3] = {m.cw[0] - m.jpos[0], m.cw[1] - m.jpos[1], m.cw[2] - m.jpos[2]};
+  T d[3];
+  if (mo) { d[0] = mo->dcj[0]; d[1] = mo->dcj[1]; d[2] = mo->dcj[2]; }
+  else once_dcj(m, d);
   T t[3];
   mv3(t, k.Rw[w], d);
   k.wc[w][0] = m.anchor[0] + t[0];
@@ -332,7 +486,8 @@ BB_HD void mass_wheel(const ModelT<T>& m, const Kin<T>& k, int w, Mass<T>& M, T*
 
 // the rest of the mass matrix from the wheel terms (mrw[w][3], IOw[w][6])
 template <typename T>
-BB_HD void mass_finish(const ModelT<T>& m, const Kin<T>& k, Mass<T>& M, const T (*mrw)[3], const T (*IOw)[6]) {
+BB_HD void mass_finish(const ModelT<T>& m, const Kin<T>& k, Mass<T>& M, const T (*mrw)[3], const T (*IOw)[6],
+                       const ModelOnce<T>* mo = nullptr) {
   T mr[3] = {m.h0[0], m.h0[1], m.h0[2]};
   T IO[6] = {m.I0O[0], m.I0O[1], m.I0O[2], m.I0O[3], m.I0O[4], m.I0O[5]};
 #pragma unroll
@@ -342,19 +497,21 @@ BB_HD void mass_finish(const ModelT<T>& m, const Kin<T>& k, Mass<T>& M, const T 
 #pragma unroll
     for (int i = 0; i < 6; i++) IO[i] += IOw[w][i];
   }
-  M.mt = m.m0 + 3 * m.mw;
+  T mt, sbd, MBrr[2];
+  if (mo) { mt = mo->mt; sbd = mo->sbd; MBrr[0] = mo->MBrr[0]; MBrr[1] = mo->MBrr[1]; }
+  else once_mass(m, mt, sbd, MBrr);
+  M.mt = mt;
   M.mr[0] = mr[0]; M.mr[1] = mr[1]; M.mr[2] = mr[2];
   T S[9] = {0, mr[2], -mr[1], -mr[2], 0, mr[0], mr[1], -mr[0], 0};  // -[mr]x
   mm3(M.Mtr, k.Rb, S);
 #pragma unroll
   for (int i = 0; i < 6; i++) M.Mrr[i] = IO[i];
-  const T dz = m.dz;
   M.mB = m.mB;
-  T SB[9] = {0, m.mB * dz, 0, -m.mB * dz, 0, 0, 0, 0, 0};  // -mB [d]x, d = (0,0,dz)
+  T SB[9] = {0, sbd, 0, -sbd, 0, 0, 0, 0, 0};  // -mB [d]x, d = (0,0,dz)
   mm3(M.MBtr, k.RB, SB);
-  M.MBrr[0] = m.IB + m.mB * dz * dz;
-  M.MBrr[1] = m.IB + m.mB * dz * dz;
-  M.MBrr[2] = m.IB;
+  M.MBrr[0] = MBrr[0];
+  M.MBrr[1] = MBrr[0];
+  M.MBrr[2] = MBrr[1];
 }
 
 template <typename T>
@@ -460,10 +617,11 @@ BB_HD void bias_base_motion(const ModelT<T>& m, const Kin<T>& k, const T* v, T* 
 // wheel w's RNE force (fa; fl) about the base origin; returns qfrc_bias[6+w]
 template <typename T>
 BB_HD T bias_wheel(const ModelT<T>& m, const Kin<T>& k, const T* Iw, const T* v, int w, const T* w0, const T* vl,
-                   const T* a0, T* fa, T* fl) {
+                   const T* a0, T* fa, T* fl, const ModelOnce<T>* mo = nullptr) {
   const T* u = m.u[w];
-  T au[3];
-  cross3(au, m.anchor, u);           // S = (u; anchor x u)
+  T au[3];                           // S = (u; anchor x u)
+  if (mo) { const T* a = mo->au[w]; au[0] = a[0]; au[1] = a[1]; au[2] = a[2]; }
+  else once_au(m, w, au);
   T qd = v[6 + w];
   T Vw[3] = {w0[0] + qd * u[0], w0[1] + qd * u[1], w0[2] + qd * u[2]};
   T Vv[3] = {vl[0] + qd * au[0], vl[1] + qd * au[1], vl[2] + qd * au[2]};
@@ -481,18 +639,23 @@ BB_HD T bias_wheel(const ModelT<T>& m, const Kin<T>& k, const T* Iw, const T* v,
 // qfrc_bias from the wheel forces fw[w] = (fa; fl): base composite, the
 // wheel sums in wheel order, and the ball (bias[6..8] are set by the caller)
 template <typename T>
-BB_HD void bias_finish(const ModelT<T>& m, const Kin<T>& k, const T* v, const T (*fw)[6], T* bias) {
+BB_HD void bias_finish(const ModelT<T>& m, const Kin<T>& k, const T* v, const T (*fw)[6], T* bias,
+                       const ModelOnce<T>* mo = nullptr) {
   T w0[3], vl[3], a0[3], t[3];
   bias_base_motion(m, k, v, w0, vl, a0);
   const T zero[3] = {0, 0, 0};
   // base composite: mass m0, COM h0/m0, inertia about COM derived from I0O
   T Fa[3], Fl[3];
   {
-    T c0[3] = {m.h0[0] / m.m0, m.h0[1] / m.m0, m.h0[2] / m.m0};
-    T cc = dot3(c0, c0);
-    T Ic[6] = {m.I0O[0] - m.m0 * (cc - c0[0] * c0[0]), m.I0O[1] - m.m0 * (cc - c0[1] * c0[1]),
-               m.I0O[2] - m.m0 * (cc - c0[2] * c0[2]), m.I0O[3] + m.m0 * c0[0] * c0[1],
-               m.I0O[4] + m.m0 * c0[0] * c0[2], m.I0O[5] + m.m0 * c0[1] * c0[2]};
+    T c0[3], Ic[6];
+    if (mo) {
+#pragma unroll
+      for (int i = 0; i < 3; i++) c0[i] = mo->bc[0][i];
+#pragma unroll
+      for (int i = 0; i < 6; i++) Ic[i] = mo->bI[0][i];
+    } else {
+      once_base_com(m, c0, Ic);
+    }
     body_force(m.m0, c0, Ic, zero, a0, w0, vl, Fa, Fl);
   }
 #pragma unroll
@@ -508,12 +671,58 @@ BB_HD void bias_finish(const ModelT<T>& m, const Kin<T>& k, const T* v, const T 
   mtv3(vB, k.RB, v + 9);
   cross3(t, vB, wB);
   T aB[3] = {m.grav * k.RB[6] + t[0], m.grav * k.RB[7] + t[1], m.grav * k.RB[8] + t[2]};
-  T cB[3] = {0, 0, m.dz};
-  T IcB[6] = {m.IB, m.IB, m.IB, 0, 0, 0};
+  T cB[3], IcB[6];
+  once_ball_com(m, cB, IcB);
   T fa[3], fl[3];
   body_force(m.mB, cB, IcB, zero, aB, wB, vB, fa, fl);
   mv3(bias + 9, k.RB, fl);
   bias[12] = fa[0]; bias[13] = fa[1]; bias[14] = fa[2];
+}
+
+// bias_finish for one half of a team: the base composite with the wheel sums (hi = false: out =
+// bias[0..5]) or the ball (out = bias[9..14]).  One body_force on the half's operands; k and v
+// are addressed by half (team-shared memory on the device).
+template <typename T>
+BB_HD void bias_finish_half(const ModelT<T>& m, const Kin<T>& k, const T* v, const T (*fw)[6], bool hi, T* out,
+                            const ModelOnce<T>* mo = nullptr) {
+  const T* R = hi ? k.RB : k.Rb;
+  const T* vlin = v + half_vlin(hi);
+  const T* vang = v + half_vang(hi);
+  // bias_base_motion, on this half's frame and velocity
+  T w0[3] = {vang[0], vang[1], vang[2]}, vl[3], t[3];
+  mtv3(vl, R, vlin);
+  cross3(t, vl, w0);
+  T a0[3] = {m.grav * R[6] + t[0], m.grav * R[7] + t[1], m.grav * R[8] + t[2]};
+  const T zero[3] = {0, 0, 0};
+  T Fa[3], Fl[3];
+  T c[3], Ic[6], mass;
+  if (mo) {  // the two operand sets side by side: one address select
+    const int b = hi ? 1 : 0;
+#pragma unroll
+    for (int i = 0; i < 3; i++) c[i] = mo->bc[b][i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) Ic[i] = mo->bI[b][i];
+    mass = mo->bm[b];
+  } else {
+    T c0[3], Ic0[6], cB[3], IcB[6];
+    once_base_com(m, c0, Ic0);
+    once_ball_com(m, cB, IcB);
+#pragma unroll
+    for (int i = 0; i < 3; i++) c[i] = hi ? cB[i] : c0[i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) Ic[i] = hi ? IcB[i] : Ic0[i];
+    mass = hi ? m.mB : m.m0;
+  }
+  body_force(mass, c, Ic, zero, a0, w0, vl, Fa, Fl);
+  if (!hi) {
+#pragma unroll
+    for (int w = 0; w < 3; w++) {
+      Fa[0] += fw[w][0]; Fa[1] += fw[w][1]; Fa[2] += fw[w][2];
+      Fl[0] += fw[w][3]; Fl[1] += fw[w][4]; Fl[2] += fw[w][5];
+    }
+  }
+  mv3(out, R, Fl);
+  out[3] = Fa[0]; out[4] = Fa[1]; out[5] = Fa[2];
 }
 
 // qfrc_bias = C(q,v) v + gravity  (mj_rne with flg_acc = 0)
@@ -607,7 +816,8 @@ struct GStore {
 
 // patched mjraw_SphereCapsule (tools/mujoco_fix.patch:11-16) + mju_makeFrame
 template <typename T>
-BB_HD void wheel_contact(const ModelT<T>& m, const Kin<T>& k, const T* v, int w, WheelCon<T>& C) {
+BB_HD void wheel_contact(const ModelT<T>& m, const Kin<T>& k, const T* v, int w, WheelCon<T>& C,
+                         const ModelOnce<T>* mo = nullptr) {
   T t[3], gp[3], ax[3], axl[3];
   mv3(t, k.Rb, k.wc[w]);
   gp[0] = k.pb[0] + t[0]; gp[1] = k.pb[1] + t[1]; gp[2] = k.pb[2] + t[2];
@@ -657,7 +867,7 @@ BB_HD void wheel_contact(const ModelT<T>& m, const Kin<T>& k, const T* v, int w,
   T imp = clampT(impedance(m, dist), T(0.0001), T(0.9999));
   T tran = m.iw_ball + m.iw_wheel[w];
   T R0 = maxT(T(1e-15), (1 - imp) * tran / imp);
-  T rr = m.fr_wheel[0] / m.fr_wheel[1];
+  T rr = mo ? mo->rr : once_rr(m);
   T R2 = R0 * rr * rr;
   C.D[0] = act / R0; C.D[1] = act / R0; C.D[2] = act / R2;
 #pragma unroll

@@ -8,6 +8,17 @@
 
 namespace bb {
 
+// ISA analysis build (-DBB_ISA_MARKS, tools/isa_phases.py --pre): the sections of the step outside
+// the Newton loop as assembler comments; nothing in any other build.
+//   1 stage state   2 kinematics   3 wheel lanes   4 mass_finish   5 bias_finish   6 collision
+//   7 stage out, dense mass, ground setup   8 solve   9 after the solve, RK sums
+//   10 mj_advance   11 obs, reward, termination (to the kernel's end)
+#if defined(BB_ISA_MARKS) && defined(__HIP_DEVICE_COMPILE__)
+#define BB_PRE(k) asm volatile("; PRE_MARK " #k);
+#else
+#define BB_PRE(k)
+#endif
+
 // Env configuration (BBotSimulation.__init__, ballbot_env.py:221-231).
 struct EnvCfg {
   int max_ep_steps;        // 4000
@@ -40,9 +51,30 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
 #endif
   Kin<T>& k = W.u.pre.k;
 #ifdef __HIP_DEVICE_COMPILE__
-  // base/ball frames on every lane, wheel w's frame on lane w
-  kinematics_base(m, q, k);
-  if (tm.tl < 3) kinematics_wheel(m, q, tm.tl, k);
+  BB_PRE(2)
+  // The FUSE kernels (the fast step and multi-step kernels, which have the registers for it and
+  // stage ModelOnce beside the model) take the pre-phase's shorter forms; the kernels at the
+  // 512-register limit keep the serial text, as they keep the plain solve.
+  // model-only terms from the staged ModelOnce (bb_physics.h) instead of their expressions
+  const ModelOnce<T>* mo = nullptr;
+#if BB_ONCE
+  if constexpr (FUSE) mo = &once_of(m);
+#endif
+  // twin forms (bb_physics.h): lanes 0-7 of a 16-lane team take the base, lanes 8-15 the ball
+  const bool twin = FUSE && tm.L == TWIN_L;
+  const bool hi = (tm.tl & 8) != 0;
+  (void)twin; (void)hi;
+  // base/ball frames on every lane (twin: one per half), wheel w's frame on lane w
+#if BB_TWIN_KIN
+  if (twin) {
+    T qn[4];
+    kinematics_half(m, q, hi, k, qn);
+    // the stage out's quat_b is the base half's normalised quaternion (same expression, same input)
+    if (so && !hi) { so->quat_b[0] = qn[0]; so->quat_b[1] = qn[1]; so->quat_b[2] = qn[2]; so->quat_b[3] = qn[3]; }
+  } else
+#endif
+    kinematics_base(m, q, k);
+  if (tm.tl < 3) kinematics_wheel(m, q, tm.tl, k, mo);
   team_sync();
 #else
   kinematics(m, q, k);
@@ -57,24 +89,39 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
     T (*IOw)[6] = reinterpret_cast<T (*)[6]>(W.H + 9);
     T (*fw)[6] = reinterpret_cast<T (*)[6]>(W.H + 27);
     static_assert(NH >= 45, "per-wheel terms do not fit W.H");
+    BB_PRE(3)
     if (tm.tl < 3) {
       const int w = tm.tl;
       mass_wheel(m, k, w, M, W.u.pre.Iw[w], mrw[w], IOw[w]);
       T w0[3], vl[3], a0[3];
       bias_base_motion(m, k, v, w0, vl, a0);
-      const T qb = -bias_wheel(m, k, W.u.pre.Iw[w], v, w, w0, vl, a0, fw[w], fw[w] + 3);
+      const T qb = -bias_wheel(m, k, W.u.pre.Iw[w], v, w, w0, vl, a0, fw[w], fw[w] + 3, mo);
       const T cw = w == 0 ? ctrl[0] : (w == 1 ? ctrl[1] : ctrl[2]);  // no dynamic index into registers
       W.qfs[6 + w] = qb + (-m.damping * v[6 + w] + cw);
-      wheel_contact(m, k, v, w, W.wc[w]);  // read after the solve's team_sync
+      wheel_contact(m, k, v, w, W.wc[w], mo);  // read after the solve's team_sync
     }
     team_sync();
-    mass_finish(m, k, M, mrw, IOw);
+    BB_PRE(4)
+    mass_finish(m, k, M, mrw, IOw, mo);
+    BB_PRE(5)
     // qfrc_smooth = -bias + passive + actuation, straight to the workspace
-    T qfs[NV];
-    bias_finish(m, k, v, fw, qfs);
+#if BB_TWIN_BIAS
+    if (twin) {
+      // each half its own body's six entries; W.vi holds v (copied above if it came from elsewhere)
+      T b6[6];
+      bias_finish_half(m, k, W.vi, fw, hi, b6, mo);
+      T* qo = W.qfs + half_vlin(hi);
 #pragma unroll
-    for (int i = 0; i < NV; i++)
-      if (i < 6 || i > 8) W.qfs[i] = -qfs[i];
+      for (int i = 0; i < 6; i++) qo[i] = -b6[i];
+    } else
+#endif
+    {
+      T qfs[NV];
+      bias_finish(m, k, v, fw, qfs, mo);
+#pragma unroll
+      for (int i = 0; i < NV; i++)
+        if (i < 6 || i > 8) W.qfs[i] = -qfs[i];
+    }
     team_sync();  // W.H free again (candidate list of the body collision)
   }
 #else
@@ -99,7 +146,8 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
   const unsigned long long f_t1 = clock64();
 #endif
 #ifdef __HIP_DEVICE_COMPILE__
-  const int ng = tr.hf ? t16::collide_team(m, k, v, tr.hf, tr.size_z, W.g, &overflow, tm.tl) : 0;
+  BB_PRE(6)
+  const int ng = tr.hf ? t16::collide_team(m, k, v, tr.hf, tr.size_z, W.g, &overflow, tm.tl, mo) : 0;
   int nb = 0;
   if constexpr (BODY) {
 #if defined(BB_PHASE_CLOCKS)
@@ -125,7 +173,7 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
   } else {
     // fast path: no base-tree contact support compiled in; configurations that
     // could have one abort here and are re-run by the full kernel
-    if (t16::body_candidates(m, k, tr.hf, tr.size_z, tr.hz, tm.tl)) return -1;
+    if (t16::body_candidates(m, k, tr.hf, tr.size_z, tr.hz, tm.tl, mo)) return -1;
   }
 #else
   const int ng = tr.hf ? collide_ground(m, k, v, tr.hf, tr.size_z, st, &overflow) : 0;
@@ -138,14 +186,21 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
     atomicAdd(&bb_phase_cycles[10], 1ull);
   }
 #endif
+  BB_PRE(7)
 #pragma unroll
   for (int i = 0; i < 9; i++) { W.P.Rb[i] = k.Rb[i]; W.P.RB[i] = k.RB[i]; }  // Jacobian rebuilds in the solve
 #pragma unroll
   for (int i = 0; i < 3; i++) { W.P.pb[i] = k.pb[i]; W.P.pB[i] = k.pB[i]; }
   if (so) {
-    T qb[4] = {q[3], q[4], q[5], q[6]};
-    qnormalize(qb);
-    so->quat_b[0] = qb[0]; so->quat_b[1] = qb[1]; so->quat_b[2] = qb[2]; so->quat_b[3] = qb[3];
+    bool have_qb = false;
+#if BB_TWIN_KIN && defined(__HIP_DEVICE_COMPILE__)
+    have_qb = FUSE && tm.L == TWIN_L;  // written with the base half's kinematics
+#endif
+    if (!have_qb) {
+      T qb[4] = {q[3], q[4], q[5], q[6]};
+      qnormalize(qb);
+      so->quat_b[0] = qb[0]; so->quat_b[1] = qb[1]; so->quat_b[2] = qb[2]; so->quat_b[3] = qb[3];
+    }
     mv3(so->w_world, k.Rb, v + 3);
     // subtree_com[base] - xpos[base] = Rb * mr / mt
     T cl[3] = {M.mr[0] / M.mt, M.mr[1] / M.mt, M.mr[2] / M.mt}, cw[3], t[3];
@@ -186,7 +241,9 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
     team_sync();
   }
 #endif
+  BB_PRE(8)
   const int it = t16::solve16<BODY, FUSE>(m, W, ng, nb, acc, tm.tl);
+  BB_PRE(9)
 #if defined(BB_PHASE_CLOCKS)
   if (BODY && tm.tl == 0) {  // full-kernel solve cycles and Newton iterations
     atomicAdd(&bb_phase_cycles[15], clock64() - s_t0);
@@ -236,12 +293,44 @@ BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const Terra
 #pragma unroll 1
   for (int stage = 0; stage < 4; stage++) {
     const T a = stage == 3 ? T(1) : T(0.5);  // RK4 Butcher A (sub-diagonal)
+    BB_PRE(1)
     {
       // stage state X0 (+) h a (v_prev, a_prev), kept in the workspace so that
       // nothing but the warm start stays in registers across the solve
       T qi[NQ], vi[NV];
 #pragma unroll
       for (int i = 0; i < NQ; i++) qi[i] = q0[i];
+#if BB_TWIN_POS && defined(__HIP_DEVICE_COMPILE__)
+      if (FUSE && tm.L == TWIN_L) {
+        // twin form: the positions and hinge angles on every lane, each half its own quaternion
+        const bool hi = (tm.tl & 8) != 0;
+        T qh[4];
+        if (stage == 0) {
+#pragma unroll
+          for (int i = 0; i < NV; i++) vi[i] = v0[i];
+#pragma unroll
+          for (int i = 0; i < 4; i++) qh[i] = q0[half_quat(hi) + i];
+        } else {
+          T dv[NV];
+#pragma unroll
+          for (int i = 0; i < NV; i++) { dv[i] = a * W.vi[i]; vi[i] = v0[i] + h * a * warm[i]; }  // W.vi: previous stage
+          integrate_pos_lin(qi, dv, h);
+          const T* wp = W.vi + half_vang(hi);
+          const T wh[3] = {a * wp[0], a * wp[1], a * wp[2]};
+          integrate_quat_half(q0 + half_quat(hi), wh, h, qh);
+        }
+        team_sync();
+#pragma unroll
+        for (int i = 0; i < NQ; i++)
+          if (i < 3 || (i >= 7 && i < 13)) W.u.pre.qi[i] = qi[i];
+        T* qo = W.u.pre.qi + half_quat(hi);
+#pragma unroll
+        for (int i = 0; i < 4; i++) qo[i] = qh[i];
+#pragma unroll
+        for (int i = 0; i < NV; i++) W.vi[i] = vi[i];
+      } else
+#endif
+      {
       if (stage == 0) {
 #pragma unroll
         for (int i = 0; i < NV; i++) vi[i] = v0[i];
@@ -256,6 +345,7 @@ BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const Terra
       for (int i = 0; i < NQ; i++) W.u.pre.qi[i] = qi[i];
 #pragma unroll
       for (int i = 0; i < NV; i++) W.vi[i] = vi[i];
+      }
     }
     // the solve's warm start / result in registers for this forward only
     // (warm may live in the workspace, see step_kernel)
@@ -303,9 +393,31 @@ BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const Terra
     }
   }
   team_sync();
+  BB_PRE(10)
   // mj_advance: qvel = v0 + h*qacc_rk ; qpos = q0 (+) h*v_rk
 #pragma unroll
   for (int i = 0; i < NV; i++) v[i] = v0[i] + h * as[i];
+#if BB_TWIN_POS && defined(__HIP_DEVICE_COMPILE__)
+  if (FUSE && tm.L == TWIN_L) {
+    // twin form; q is the team's shared state (every device caller keeps it in the workspace),
+    // so each half stores its own quaternion and a team_sync shows it to the other half
+    const bool hi = (tm.tl & 8) != 0;
+#pragma unroll
+    for (int i = 0; i < NQ; i++)
+      if (i < 3 || (i >= 7 && i < 13)) q[i] = q0[i];
+    T vv[NV];
+#pragma unroll
+    for (int i = 0; i < NV; i++) vv[i] = vs[i];
+    integrate_pos_lin(q, vv, h);
+    T qh[4];
+    integrate_quat_half(q0 + half_quat(hi), vs + half_vang(hi), h, qh);
+    T* qo = q + half_quat(hi);
+#pragma unroll
+    for (int i = 0; i < 4; i++) qo[i] = qh[i];
+    team_sync();
+    return iters;
+  }
+#endif
 #pragma unroll
   for (int i = 0; i < NQ; i++) q[i] = q0[i];
   T vv[NV];
@@ -383,6 +495,7 @@ BB_HD int env_step(const ModelT<T>& m, const EnvCfg& cfg, T* q, T* v, T* warm, i
   StageOut<T>& so = W.so;  // team-shared (LDS): not register-resident across the solves
   bool acc_reset = false;
   int it = rk4_step<T, BODY, FUSE>(m, q, v, warm, ctrl, tr, W, so, tm, &acc_reset);
+  BB_PRE(11)
   if (it < 0) return F_SLOWPATH;
   if (iters) *iters = it;
   if (acc_reset) flags |= F_DIVERGED;

@@ -577,7 +577,12 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
   const bool rowl = tl < NV;
   const int row = rowl ? tl : NV - 1;
   const T muw = m.fr_wheel[0];
-  const T kdw = T(1) / (muw * muw * (1 + muw * muw));
+  T kdw;
+#if BB_ONCE
+  if constexpr (FUSE) kdw = once_of(m).kdw;  // the FUSE kernels stage ModelOnce (bb_step.h: forward)
+  else
+#endif
+    kdw = once_kdw(m);
   const T qfs_i = W.qfs[row];
   const int gcol = row - 9;  // this row's ball dof (rows 9..14), else < 0
   // the wheels' f and C (packed C[6], f[3] each) go through LDS (the wf + hg
@@ -1289,7 +1294,8 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
 // (and the MAXG cap) is exactly the serial one.
 template <typename T>
 __device__ __forceinline__ int collide_team(const ModelT<T>& m, const Kin<T>& k, const T* v, const float* hf,
-                                            T size_z, T* g, int* overflow, int tl) {
+                                            T size_z, T* g, int* overflow, int tl,
+                                            const ModelOnce<T>* mo = nullptr) {
   const T r = m.ball_r;
   const T* c = k.c;
   const T sx = m.hf_sx, sy = m.hf_sy, zb = m.hf_bottom;
@@ -1308,7 +1314,9 @@ __device__ __forceinline__ int collide_team(const ModelT<T>& m, const Kin<T>& k,
   const int ncol = cmax - cmin + 1;
   const int np = 2 * ncol - 2;            // prisms per grid row
   const int total = (rmax - rmin) * (np > 0 ? np : 0);
-  const T dx = 2 * sx / N1, dy = 2 * sy / N1;
+  T dx, dy;
+  if (mo) { dx = mo->dx; dy = mo->dy; }
+  else once_pitch(m, dx, dy);
   (void)v;
   const int team_shift = team_shift_of(L);
   int ng = 0;
@@ -1434,7 +1442,8 @@ __device__ __forceinline__ bool prism_may_hit(const Reach<T>& g, const T (&V)[3]
 // the geom's AABB is skipped), so "no" is exact and "yes" sends the env to the
 // full kernel.  Team-uniform result.
 template <typename T>
-__device__ bool body_candidates(const ModelT<T>& m, const Kin<T>& k, const float* hf, T size_z, T hz, int tl) {
+__device__ bool body_candidates(const ModelT<T>& m, const Kin<T>& k, const float* hf, T size_z, T hz, int tl,
+                                const ModelOnce<T>* mo = nullptr) {
   bool cand = false;
   // lane gi < 6 places geom gi once (lanes 0..2 also test it against the
   // ball) and screens it against the terrain: its AABB must reach the
@@ -1490,7 +1499,9 @@ __device__ bool body_candidates(const ModelT<T>& m, const Kin<T>& k, const float
       // the full kernel's prisms (cells [rmin, rmax) x [cmin, cmax), two
       // triangles each) under its own two prunes: a candidate iff the exact
       // prism test would run on at least one of them
-      const T dx = 2 * sx / N1, dy = 2 * sy / N1;
+      T dx, dy;
+      if (mo) { dx = mo->dx; dy = mo->dy; }
+      else once_pitch(m, dx, dy);
       const int nc = cmax - cmin, total = (rmax - rmin) * nc;
       for (int i = tl; i < total && !cand; i += L) {
         const int ri = rmin + i / nc, ci = cmin + i % nc;
@@ -1556,7 +1567,8 @@ __device__ int collide_body_team(const ModelT<T>& m, const Kin<T>& k, const floa
   if (hf) {
     const T sx = m.hf_sx, sy = m.hf_sy, zb = m.hf_bottom;
     const int N1 = HF_N - 1;
-    const T dx = 2 * sx / N1, dy = 2 * sy / N1;
+    T dx, dy;
+    once_pitch(m, dx, dy);
     int nc = 0;  // candidates pending in cand[]
     int pair_n[6] = {0, 0, 0, 0, 0, 0};  // contacts so far per hfield pair (team-uniform)
     auto vertices = [&](int rr, int p, T (&V)[3][3]) {

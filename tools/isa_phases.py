@@ -13,6 +13,17 @@ between the branch and its target), attributed to the branch's phase.
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DBB_ISA_MARKS -I openballbot-rl_amd/csrc \
       --cuda-device-only -S -o /tmp/bbk.s openballbot-rl_amd/csrc/bb_kernels.hip
   python tools/isa_phases.py /tmp/bbk.s
+
+With --pre the second mark family is counted instead: the `; PRE_MARK k` comments of bb_step.h
+(BB_PRE) that cut the whole step outside the Newton loop into sections.  Per kernel (--kernel
+SUBSTRING of the mangled name, default the fp64 fast multi-step kernel) and section: all
+instructions, VALU, FP64 (v_*_f64), rcp + rsq, v_readlane / v_writelane (SGPR spills) and AGPR
+moves (v_accvgpr_*).  A section is the text from its mark to the next mark of either family; the
+code before the first mark is the kernel prologue, the solve's PHASE_MARK sections are summed
+into "solve".  Where the compiler duplicated a section (both arms of the team-size test, a peeled
+loop) the copies add up, so the serial fall-back of the twin forms is listed with them.
+
+  python tools/isa_phases.py --pre /tmp/bbk.s
 """
 import re
 import sys
@@ -107,5 +118,68 @@ def main(path):
               (tot["valu"], tot["dpp"], tot["lds"], tot["vmem"], tot["salu"], tot["wait"], tot["rwait"], tot["xbr"], tot["short"]))
 
 
+PRE_NAMES = {0: "kernel prologue", 1: "stage state", 2: "kinematics", 3: "wheel lanes", 4: "mass_finish",
+             5: "bias_finish", 6: "collision", 7: "stage out, dense mass, ground setup", 8: "solve",
+             9: "after the solve, RK sums", 10: "mj_advance", 11: "obs, reward, termination, stores"}
+
+
+def pre_main(path, want):
+    func, cur, counts = None, None, {}
+    for line in open(path):
+        m = re.match(r"^(_Z[^:\s]+):", line)
+        if m:
+            func, cur = m.group(1), 0
+            continue
+        if func is None or want not in func:
+            continue
+        m = re.search(r"; PRE_MARK (\d+)", line)
+        if m:
+            cur = int(m.group(1))
+            continue
+        m = re.search(r"; PHASE_MARK (\d+)", line)
+        if m:
+            cur = 9 if int(m.group(1)) == 7 else 8  # PH(7): the solver's exit
+            continue
+        s = line.strip()
+        if not s or s.startswith((";", ".")) or s.endswith(":"):
+            continue
+        if s.startswith("s_endpgm"):
+            func = None
+            continue
+        op = s.split()[0]
+        c = counts.setdefault(func, {}).setdefault(cur, Counter())
+        c["all"] += 1
+        if op.startswith("v_"):
+            c["valu"] += 1
+        if op.startswith("v_") and "_f64" in op:
+            c["fp64"] += 1
+        if op.startswith(("v_rcp", "v_rsq")):
+            c["rcp"] += 1
+        if op.startswith(("v_readlane", "v_writelane", "v_readfirstlane")):
+            c["lane"] += 1
+        if op.startswith("v_accvgpr"):
+            c["agpr"] += 1
+    for func, secs in counts.items():
+        print(func[:100])
+        print("  %-38s %6s %6s %6s %8s %6s %6s" % ("section", "all", "VALU", "FP64", "rcp+rsq", "lane", "AGPR"))
+        tot = Counter()
+        for k in sorted(secs):
+            c = secs[k]
+            tot.update(c)
+            print("  %-38s %6d %6d %6d %8d %6d %6d" % (PRE_NAMES.get(k, str(k)), c["all"], c["valu"], c["fp64"], c["rcp"],
+                                                       c["lane"], c["agpr"]))
+        print("  %-38s %6d %6d %6d %8d %6d %6d" % ("total", tot["all"], tot["valu"], tot["fp64"], tot["rcp"], tot["lane"],
+                                                   tot["agpr"]))
+
+
 if __name__ == "__main__":
-    main(sys.argv[1])
+    if "--pre" in sys.argv:
+        args = [a for a in sys.argv[1:] if a != "--pre"]
+        kern = "multi_step_kernelIdLb0E"
+        if "--kernel" in args:
+            i = args.index("--kernel")
+            kern = args[i + 1]
+            del args[i:i + 2]
+        pre_main(args[0], kern)
+    else:
+        main(sys.argv[1])
