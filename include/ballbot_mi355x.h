@@ -27,6 +27,7 @@
  *   bb_rollout_track SB3 collect_rollouts / Monitor episode bookkeeping
  *   bb_rollout       a whole SB3 collect_rollouts (policy + step + bookkeeping) in one launch
  *   bb_reward_terms  reward_term_1_hist / reward_term_2_hist of _save_logs  ballbot_env.py:929-937, 673-699
+ *   bb_pid_act       PID.act, the balance controller             controllers/pid.py:61-101
  *   bb_depth_encoder frozen rgbd encoder of the camera policy, fused
  *   bb_gae           SB3 RolloutBuffer.compute_returns_and_advantage (PPO)
  *   bb_forward       mujoco.mj_forward (diagnostic)             ballbot_env.py:525,620
@@ -340,6 +341,37 @@ int bb_rollout(bb_handle* h, const bb_rollout_args* args, void* stream);
  * sync, no host read: graph-capturable. */
 int bb_reward_terms(bb_handle* h, const float* obs_dev, const uint8_t* flags_dev, int k_steps, float* terms_dev,
                     int64_t terms_rows, int64_t* book_dev, void* stream);
+/* The reference's balance controller for n envs (ballbot_gym/controllers/pid.py:61-101, the install
+ * check scripts/test_pid.py:22-63): PID on the pitch / roll error, mixed into three motor commands.
+ * Per row, in the reference's float32 operation order without fused multiply-adds: clear the state if
+ * (reset_dev[e] & reset_mask) != 0; e = (setpoint_p - pitch, setpoint_r - roll); integral += e dt;
+ * d = (e - prev_err) / dt; u = k_p e + k_i integral + k_d d; prev_err = e; motor k = u[1] c_k +
+ * u[0] s_k with c_k, s_k = float(cos / sin(deg2rad(0, 120, 240))), clamped to +-limit (the reference's
+ * limit is 10).  Only the third row of R enters: roll = atan2(R21, R22), pitch = atan2(-R20,
+ * sqrt(R21^2 + R22^2)).  BB_PID_ROTVEC rows give that row by Rodrigues in double (identity below
+ * 1e-14 rad), rounded to float; the two angles are taken in double from the float row and rounded
+ * once each, so they are within half an ulp of exact.  angle_deg = float(acos(clamp(R22)) 180 / pi),
+ * the acos in double.  A NaN row yields NaN in that row only.  An observation row is passed as
+ * obs_dev + 9 with stride 15.  No handle; one launch on stream, no allocation, no sync and no host
+ * read: graph-capturable.  n == 0 returns 0 and launches nothing.  (ABI 21 still holds: purely
+ * additive, detected by symbol.) */
+#define BB_PID_ROTVEC 0     /* orient rows hold a rotation vector (3 floats): obs[9:12] */
+#define BB_PID_ROTMAT 1     /* orient rows hold a row-major 3x3 rotation matrix (9 floats): PID.act's R_mat */
+#define BB_PID_MOTOR 0      /* out: 3 motor commands, clamped to +-limit */
+#define BB_PID_PITCH_ROLL 1 /* out: u[2] (pitch, roll), unclamped: return_in_pitch_roll_space */
+typedef struct bb_pid_cfg {
+  float dt, k_p, k_i, k_d, limit;
+  int32_t orient_kind, space;
+} bb_pid_cfg;
+int bb_pid_act(const bb_pid_cfg* cfg,
+               const float* orient_dev, int64_t orient_stride, /* row e at orient_dev + e*stride floats; float-aligned only */
+               const float* setpoint_dev,                      /* [n][2] (pitch, roll) radians, or NULL = 0 */
+               const uint8_t* reset_dev, int reset_mask,       /* [n] or NULL */
+               float* state_dev,     /* [n][4] in/out: integral (pitch, roll), prev_err (pitch, roll) */
+               int n,
+               float* out_dev,       /* [n][3] motor space, [n][2] pitch/roll space */
+               float* angle_deg_dev, /* [n] or NULL: tilt, acos(R[2][2]) in degrees */
+               void* stream);
 /* One rollout step's episode bookkeeping (SB3 collect_rollouts + Monitor,
  * model.learn at ballbot_rl/training/train.py:284): done = (flags_dev[i] &
  * done_mask) != 0; rewards_out_dev[i] = reward_dev[i]; the float64 episode

@@ -38,6 +38,7 @@
 #include "bb_terrain.h"
 #include "bb_rollout.h"
 #include "bb_episode_log.h"
+#include "bb_pid.h"
 #include "bb_render.h"
 #include "bb_view.h"
 #include "bb_rgbd.h"
@@ -2933,6 +2934,29 @@ int bb_reward_terms(bb_handle* h, const float* obs, const uint8_t* flags, int k,
   if (launch_reward_terms(rc, obs, flags, k, h->n, terms, (long long)terms_rows, reinterpret_cast<long long*>(book),
                           (hipStream_t)stream))
     return fail("bb_reward_terms: launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
+int bb_pid_act(const bb_pid_cfg* cfg, const float* orient, int64_t orient_stride, const float* setpoint,
+               const uint8_t* reset, int reset_mask, float* state, int n, float* out, float* angle_deg, void* stream) {
+  // argument checks first (none of them touches HIP)
+  if (!cfg || !orient || !state || !out) return fail("bb_pid_act: NULL argument");
+  if (n < 0) return fail("bb_pid_act: n must be >= 0 (got %d)", n);
+  if (!(cfg->dt > 0.f)) return fail("bb_pid_act: dt must be > 0 (got %g)", (double)cfg->dt);
+  if (!(cfg->limit > 0.f)) return fail("bb_pid_act: limit must be > 0 (got %g)", (double)cfg->limit);
+  if (cfg->orient_kind != BB_PID_ROTVEC && cfg->orient_kind != BB_PID_ROTMAT)
+    return fail("bb_pid_act: orient_kind must be BB_PID_ROTVEC (0) or BB_PID_ROTMAT (1) (got %d)", cfg->orient_kind);
+  if (cfg->space != BB_PID_MOTOR && cfg->space != BB_PID_PITCH_ROLL)
+    return fail("bb_pid_act: space must be BB_PID_MOTOR (0) or BB_PID_PITCH_ROLL (1) (got %d)", cfg->space);
+  const int row = cfg->orient_kind == BB_PID_ROTMAT ? 9 : 3;
+  if (orient_stride < row)
+    return fail("bb_pid_act: orient_stride must be >= %d floats for this orient_kind (got %lld)", row,
+                (long long)orient_stride);
+  if (n == 0) return 0;
+  const PidCfg pc{cfg->dt, cfg->k_p, cfg->k_i, cfg->k_d, cfg->limit, cfg->orient_kind, cfg->space};
+  if (launch_pid_act(pc, orient, (long long)orient_stride, setpoint, reset, reset_mask, state, n, out, angle_deg,
+                     (hipStream_t)stream))
+    return fail("bb_pid_act: launch failed: %s", hipGetErrorString(hipGetLastError()));
   return 0;
 }
 
