@@ -28,6 +28,7 @@
  *   bb_rollout       a whole SB3 collect_rollouts (policy + step + bookkeeping) in one launch
  *   bb_reward_terms  reward_term_1_hist / reward_term_2_hist of _save_logs  ballbot_env.py:929-937, 673-699
  *   bb_pid_act       PID.act, the balance controller             controllers/pid.py:61-101
+ *   bb_pid_rollout   the install check's loop (PID.act + env.step) in one launch   scripts/test_pid.py:38-65
  *   bb_depth_encoder frozen rgbd encoder of the camera policy, fused
  *   bb_gae           SB3 RolloutBuffer.compute_returns_and_advantage (PPO)
  *   bb_forward       mujoco.mj_forward (diagnostic)             ballbot_env.py:525,620
@@ -372,6 +373,62 @@ int bb_pid_act(const bb_pid_cfg* cfg,
                float* out_dev,       /* [n][3] motor space, [n][2] pitch/roll space */
                float* angle_deg_dev, /* [n] or NULL: tilt, acos(R[2][2]) in degrees */
                void* stream);
+/* The balance loop of the reference's install check (scripts/test_pid.py:38-65: PID.act,
+ * controllers/pid.py:61-101, then env.step, ballbot_env.py:903-1036) for n_steps steps of every env
+ * in ONE launch: what n_steps x (bb_pid_act on obs + 9 with reset = done & BB_DONE_TERMINATED, then
+ * bb_step on its commands) would compute, with no env waiting for the slowest env of the GPU at
+ * every step.  Step t of env e: clear the controller row if the flags of the step before have
+ * BB_DONE_TERMINATED (for t = 0 those are done[e] as passed in); run bb_pid_act's row function
+ * (the same code, so the same floats) on the carried observation with setpoint[e] or
+ * setpoint_seq[t][e] (both NULL: 0); step the env on the three commands unclipped (the step scales
+ * and clips them as bb_step does), with auto_reset as given.  Afterwards state, obs, done, reward,
+ * terminal_obs and pos2d hold what the n_steps-th pair of calls would have left, and the handle's
+ * state, counters and terrain draws are those of n_steps bb_step calls.
+ * Summary (all seven pointers or none): balance()'s per-env accumulators, in/out, updated per step
+ * in this order with alive as before the step -- max_angle = alive ? maximum(max_angle, angle_deg) :
+ * max_angle (a NaN propagates); steps += alive; g_tau += alive ? fl64(double(reward) * weights[t]) :
+ * 0 (two roundings, no fused multiply-add; weights[t] = gamma^t comes from the host, the kernel
+ * never calls pow); sum_pos2d = alive ? pos2d : sum_pos2d; failed |= alive & terminated & failure;
+ * alive &= !terminated.
+ * Routes: the serial multi-step forms on every bank -- two launches with the fast path's
+ * hand-overs parked (the in/out buffers carry the loop between them), or one with them inline
+ * (BB_MULTI_PARK=0).  The results are those of the per-step loop under the serial route
+ * (BB_ROUTE=1), bit for bit, on flat and relief banks alike; against a default-route handle on a
+ * relief bank (route 0) a single step agrees only within the rounding bounds that hold between the
+ * two routes, as for every serial form here.  A controller inside the relief pair or the work queue
+ * is not built.  Built-in rewards only (not BB_REWARD_NONE).  A bad argument returns < 0 before
+ * anything is launched; the handle's sticky fault (bb_check) is returned at once.  No allocation,
+ * no sync, no host read: graph-capturable.  (ABI 21 still holds: purely additive, detected by
+ * symbol.) */
+typedef struct bb_pid_rollout_args {
+  bb_pid_cfg cfg;            /* orient_kind must be BB_PID_ROTVEC, space BB_PID_MOTOR */
+  int n_steps;               /* K >= 1 */
+  const float* setpoint;     /* [n][2] (pitch, roll) or NULL */
+  const float* setpoint_seq; /* [K][n][2] or NULL; at most one of the two */
+  float* state;              /* [n][4] in/out */
+  float* obs;                /* [n][15] in: what step 0's action is computed from; out: after step K */
+  uint8_t* done;             /* [n] in: flags of the step before; out: the last step's */
+  float* reward;             /* [n] or NULL: the last step's, as bb_step leaves them */
+  float* terminal_obs;       /* [n][15] or NULL */
+  float* pos2d;              /* [n][2] or NULL */
+  /* traces, each NULL or [K][n][..]: what K (bb_pid_act, bb_step) calls would have written */
+  float* buf_actions;        /* [K][n][3] */
+  float* buf_angle_deg;      /* [K][n] */
+  float* buf_obs;            /* [K][n][15] */
+  float* buf_reward;         /* [K][n] */
+  uint8_t* buf_flags;        /* [K][n] */
+  float* buf_terminal_obs;   /* [K][n][15] */
+  float* buf_pos2d;          /* [K][n][2] */
+  /* balance()'s summary: all NULL or all set */
+  const double* weights;     /* [K] */
+  uint8_t* alive;            /* [n] in/out, 0 / 1 */
+  int64_t* steps;            /* [n] in/out */
+  uint8_t* failed;           /* [n] in/out, 0 / 1 */
+  float* max_angle;          /* [n] in/out */
+  double* g_tau;             /* [n] in/out */
+  float* sum_pos2d;          /* [n][2] in/out */
+} bb_pid_rollout_args;
+int bb_pid_rollout(bb_handle* h, const bb_pid_rollout_args* args, int auto_reset, void* stream);
 /* One rollout step's episode bookkeeping (SB3 collect_rollouts + Monitor,
  * model.learn at ballbot_rl/training/train.py:284): done = (flags_dev[i] &
  * done_mask) != 0; rewards_out_dev[i] = reward_dev[i]; the float64 episode

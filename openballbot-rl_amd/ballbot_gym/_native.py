@@ -121,6 +121,18 @@ class PIDCfg(C.Structure):
 PID_ROTVEC, PID_ROTMAT = 0, 1  # BB_PID_ROTVEC / BB_PID_ROTMAT
 PID_MOTOR, PID_PITCH_ROLL = 0, 1  # BB_PID_MOTOR / BB_PID_PITCH_ROLL
 
+PID_ROLLOUT_TRACES = ("buf_actions", "buf_angle_deg", "buf_obs", "buf_reward", "buf_flags", "buf_terminal_obs",
+                      "buf_pos2d")
+PID_ROLLOUT_SUMMARY = ("weights", "alive", "steps", "failed", "max_angle", "g_tau", "sum_pos2d")
+
+
+class PIDRolloutArgs(C.Structure):
+    """bb_pid_rollout_args (include/ballbot_mi355x.h): K steps of the PID balance loop in one launch."""
+    _fields_ = [("cfg", PIDCfg), ("n_steps", C.c_int)] + [
+        (name, C.c_void_p) for name in ("setpoint", "setpoint_seq", "state", "obs", "done", "reward", "terminal_obs",
+                                        "pos2d") + PID_ROLLOUT_TRACES + PID_ROLLOUT_SUMMARY]
+
+
 ENCODER_FIELDS = ("conv1_w", "conv1_b", "bn1_w", "bn1_b", "bn1_mean", "bn1_var", "bn1_count",
                   "conv2_w", "conv2_b", "bn2_w", "bn2_b", "bn2_mean", "bn2_var", "bn2_count",
                   "fc_w", "fc_b", "bn3_w", "bn3_b", "bn3_mean", "bn3_var", "bn3_count")
@@ -140,6 +152,7 @@ EXPORTS = [
     "bb_set_terrain_stream", "bb_get_env_terrain", "bb_kernel_times", "bb_step_multi", "bb_rollout",
     "bb_set_terrain_rng", "bb_get_terrain_rng", "bb_pair_counters", "bb_pair_env_times", "bb_check",
     "bb_reward_terms", "bb_default_view", "bb_render_view", "bb_render_rgbd", "bb_pid_act",
+    "bb_pid_rollout",
 ]
 
 ABI_VERSION = 21  # include/ballbot_mi355x.h BB_ABI_VERSION
@@ -148,7 +161,8 @@ _lib = None
 
 
 HIP_SOURCES = ("bb_kernels.hip", "bb_pair.hip", "bb_terrain.hip", "bb_rollout.hip", "bb_render.hip", "bb_view.hip",
-               "bb_rgbd.hip", "bb_ppo.hip", "bb_mlp.hip", "bb_encoder.hip", "bb_episode_log.hip", "bb_pid.hip")
+               "bb_rgbd.hip", "bb_ppo.hip", "bb_mlp.hip", "bb_encoder.hip", "bb_episode_log.hip", "bb_pid.hip",
+               "bb_pid_rollout.hip")
 # per-source flags: the relief pair's unit without MachineLICM (bb_kernels.hip: bb_pair_launch_tu)
 SOURCE_FLAGS = {"bb_pair.hip": ["-mllvm", "-disable-machine-licm"]}
 
@@ -263,6 +277,7 @@ def _load(path: Path):
     L.bb_ppo_mlp_act.argtypes = [vp, C.POINTER(C.c_int32), C.c_int64, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp,
                                  vp]
     L.bb_pid_act.argtypes = [C.POINTER(PIDCfg), vp, C.c_int64, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
+    L.bb_pid_rollout.argtypes = [vp, C.POINTER(PIDRolloutArgs), C.c_int, vp]
     L.bb_rollout_track.argtypes = [vp, vp, C.c_int, C.c_int] + [vp] * 8
     L.bb_depth_encoder_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_int64)]
     L.bb_depth_encoder.argtypes = [C.POINTER(EncoderParams), vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int,

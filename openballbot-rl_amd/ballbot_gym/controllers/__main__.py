@@ -1,6 +1,6 @@
 """The reference's install check (scripts/test_pid.py:15-65) on this build:
 
-    python -m ballbot_gym.controllers [pitch_deg roll_deg] [--num-envs 1] [--steps 25000] [--video PATH]
+    python -m ballbot_gym.controllers [pitch_deg roll_deg] [--num-envs 1] [--steps 25000] [--video PATH | --fused]
 
 Flat terrain, max_ep_steps = steps, gains 20/15/2 ("better for 500hz, but not optimal"), the optional
 setpoints in degrees.  Prints the reference's lines per env and exits with status 0 when no env failed.
@@ -23,9 +23,13 @@ def main(argv=None) -> int:
     ap.add_argument("--num-envs", type=int, default=1)
     ap.add_argument("--steps", type=int, default=25000)
     ap.add_argument("--video", default=None, metavar="PATH", help="animated PNG of env 0's world view")
+    ap.add_argument("--fused", action="store_true",
+                    help="run the loop inside the launch (bb_pid_rollout, 500 steps per launch)")
     args = ap.parse_args(argv)
     if len(args.setpoints) not in (0, 2):
         ap.error("give both setpoints (pitch_deg roll_deg) or neither")
+    if args.fused and args.video:
+        ap.error("--video renders frames between steps: it cannot be combined with --fused")
     setpoint_p, setpoint_r = (np.deg2rad(args.setpoints) if args.setpoints else (0.0, 0.0))
 
     from ballbot_gym.envs import BallbotVecEnv
@@ -42,7 +46,7 @@ def main(argv=None) -> int:
                 frames.append(e.render_view([0], 320, 240)[0])
 
         out = balance(env, pid, args.steps, setpoint_r=float(setpoint_r), setpoint_p=float(setpoint_p),
-                      callback=grab if args.video else None)
+                      callback=grab if args.video else None, fused=args.fused)
         if args.video:
             import torch
 

@@ -4,7 +4,9 @@
 (scripts/test_pid.py) and as a classical baseline.  `BatchedPID` runs the same recurrence for N envs:
 on a GPU through bb_pid_act (csrc/bb_pid.hip, one launch per call, graph-capturable), on CPU
 tensors through `pid_rows`, the vectorised float32 torch restatement that `PID` is with N = 1.
-`balance` is the loop of the reference's script on a BallbotVecEnv.
+`balance` is the loop of the reference's script on a BallbotVecEnv.  `BatchedPID.rollout` and
+`balance(fused=True)` run K steps of that loop inside one launch (bb_pid_rollout, csrc/bb_kernels.hip:
+pid_rollout_kernel), with the per-step loop's bits under the env's serial route.
 
 Angles: only the third row of R enters, roll = atan2(R21, R22), pitch = atan2(-R20,
 sqrt(R21^2 + R22^2)).  A rotation vector gives that row by Rodrigues in float64, rounded to float32.
@@ -230,6 +232,82 @@ class BatchedPID:
                     "bb_pid_act")
             return self.actions, self.angle_deg
 
+    # -------------------------------------------------------------- rollout
+    # trace name -> (bb_pid_rollout_args field, trailing shape, dtype)
+    TRACES = {"actions": ("buf_actions", (3,), torch.float32), "angle_deg": ("buf_angle_deg", (), torch.float32),
+              "obs": ("buf_obs", (15,), torch.float32), "reward": ("buf_reward", (), torch.float32),
+              "done": ("buf_flags", (), torch.uint8), "terminal_obs": ("buf_terminal_obs", (15,), torch.float32),
+              "pos2d": ("buf_pos2d", (2,), torch.float32)}
+
+    def _rollout_setpoints(self, k: int, setpoint_r, setpoint_p):
+        """-> the [K, N, 2] schedule, or None after filling the controller's own [N, 2] buffer."""
+        n = self.num_envs
+        sched = [isinstance(v, torch.Tensor) and v.dim() == 2 for v in (setpoint_p, setpoint_r)]
+        for v in (setpoint_p, setpoint_r):
+            if isinstance(v, torch.Tensor) and tuple(v.shape) not in ((n,), (k, n)):
+                raise ValueError(f"a setpoint must be a float, f32[{n}] or f32[{k}, {n}], got shape {tuple(v.shape)}")
+        if not any(sched):
+            self._set_setpoints(setpoint_r, setpoint_p)
+            return None
+        seq = torch.empty(k, n, 2, dtype=torch.float32, device=self.device)
+        for col, v in ((0, setpoint_p), (1, setpoint_r)):
+            seq[:, :, col] = v.to(device=self.device, dtype=torch.float32) if isinstance(v, torch.Tensor) else float(v)
+        self.setpoint.copy_(seq[-1])  # where K act() calls would have left the controller's setpoints
+        self._setpoint_host = None
+        return seq
+
+    def _launch_rollout(self, k: int, setpoint_r, setpoint_p, traces: Dict[str, torch.Tensor], summary=None) -> None:
+        """One bb_pid_rollout launch of k steps; summary: the seven tensors of PID_ROLLOUT_SUMMARY, in order."""
+        if self.env is None:
+            raise ValueError("rollout() needs a controller bound to an env (BatchedPID(env, ...))")
+        if self.device.type != "cuda":
+            raise ValueError("rollout() runs on a GPU; this controller is on the CPU (use act() and env.step())")
+        if self.space != "motor":
+            raise ValueError('rollout() steps the env on motor commands: the controller must have space="motor"')
+        if int(k) < 1:
+            raise ValueError(f"k_steps must be >= 1, got {k}")
+        from .. import _native as N
+
+        with torch.no_grad():
+            env, k = self.env, int(k)
+            seq = self._rollout_setpoints(k, setpoint_r, setpoint_p)
+            p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            args = N.PIDRolloutArgs()
+            args.cfg = N.PIDCfg(self.dt, self.k_p, self.k_i, self.k_d, self.limit, N.PID_ROTVEC, N.PID_MOTOR)
+            args.n_steps = k
+            args.setpoint, args.setpoint_seq = (None, p(seq)) if seq is not None else (p(self.setpoint), None)
+            args.state, args.obs, args.done = p(self.state), p(env.obs), p(env.done)
+            args.reward, args.terminal_obs, args.pos2d = p(env.reward), p(env.terminal_obs), p(env.pos2d)
+            for name, t in traces.items():
+                setattr(args, self.TRACES[name][0], p(t))
+            if summary is not None:
+                for name, t in zip(N.PID_ROLLOUT_SUMMARY, summary):
+                    setattr(args, name, p(t))
+            env.run_pid_rollout(args)
+
+    def rollout(self, k_steps: int, setpoint_r=0.0, setpoint_p=0.0, trace=(), out: Optional[dict] = None) -> dict:
+        """k_steps x (act, env.step) of the bound env in ONE launch (bb_pid_rollout), on the env's own
+        obs / done / reward / terminal_obs / pos2d buffers and this controller's `state`: afterwards the
+        env and the controller's state and setpoints are where k_steps act() + step() calls would have left
+        them, bit for bit under the env's serial route, so the two forms can be mixed freely.  (The
+        `actions` / `angle_deg` output buffers of act() are not rewritten: trace them.)  Setpoints in
+        radians: floats, f32[N], or f32[K, N] for a schedule (row t at step t).  `trace` names the
+        per-step buffers to keep, from "actions" [K,N,3], "angle_deg" [K,N], "obs" [K,N,15], "reward"
+        [K,N], "done" [K,N] uint8, "terminal_obs" [K,N,15], "pos2d" [K,N,2]; -> the dict of them.  `out`
+        (a dict returned before, same K and names) is refilled instead of allocating.  An env that
+        records episode logs needs "terminal_obs" and "done".  No sync, no host read."""
+        names = (trace,) if isinstance(trace, str) else tuple(trace)
+        for name in names:
+            if name not in self.TRACES:
+                raise ValueError(f"unknown trace {name!r}; choose from {sorted(self.TRACES)}")
+        k, n = int(k_steps), self.num_envs
+        reuse = out is not None and set(out) == set(names) and all(int(t.shape[0]) == k for t in out.values())
+        if not reuse:
+            out = {name: torch.empty((max(k, 0), n) + self.TRACES[name][1], dtype=self.TRACES[name][2],
+                                     device=self.device) for name in names}
+        self._launch_rollout(k, setpoint_r, setpoint_p, out)
+        return out
+
     def _run_torch(self, rows: torch.Tensor, kind: int, reset):
         if reset is not None:
             self.reset(reset)
@@ -243,19 +321,47 @@ class BatchedPID:
 
 
 def balance(env, controller, n_steps: int, setpoint_r=0.0, setpoint_p=0.0, gamma: float = 0.999999,
-            callback=None) -> Dict[str, np.ndarray]:
+            callback=None, fused: bool = False, chunk: int = 500) -> Dict[str, np.ndarray]:
     """The loop of the reference's scripts/test_pid.py:38-65 on a BallbotVecEnv: reset, then n_steps of
     controller.act and env.step.  Each env is followed until its first episode ends; everything is
     accumulated on the device and read once at the end.  `callback(step, env)`, if given, runs after
-    every step (the install check renders its video frames there).  -> per env
+    every step (the install check renders its video frames there).  `fused`: the same loop as
+    ceil(n_steps / chunk) bb_pid_rollout launches with the accumulators inside (a controller bound to
+    a GPU env, motor space; no callback) -- the same dict, bit for bit under the env's serial route;
+    `chunk` bounds how long one launch holds the GPU.  -> per env
       "steps"     steps survived (n_steps when the episode never ended),
       "failed"    the episode ended on the failure flag (tilt past max_allowed_tilt),
       "max_angle_deg" the largest tilt the controller saw,
       "G_tau"     sum_t gamma^t reward_t (float64),
       "pos2d"     the last base position of the episode."""
+    if fused and callback is not None:
+        raise ValueError("balance(fused=True) runs whole chunks of steps per launch: a per-step callback needs "
+                         "fused=False")
+    if fused and int(chunk) < 1:
+        raise ValueError(f"chunk must be >= 1, got {chunk}")
     obs, _ = env.reset()
     controller.reset()
     n, dev = env.num_envs, env.device
+    if fused:
+        total, chunk = int(n_steps), int(chunk)
+        alive = torch.ones(n, dtype=torch.uint8, device=dev)
+        steps = torch.zeros(n, dtype=torch.int64, device=dev)
+        failed = torch.zeros(n, dtype=torch.uint8, device=dev)
+        max_angle = torch.zeros(n, dtype=torch.float32, device=dev)
+        g_tau = torch.zeros(n, dtype=torch.float64, device=dev)
+        pos = torch.zeros(n, 2, dtype=torch.float32, device=dev)
+        # gamma^t by Python's pow, as the unfused loop's `gamma ** t`: the kernel never calls pow
+        weights = torch.tensor([gamma ** t for t in range(total)], dtype=torch.float64).to(dev)
+        for t0 in range(0, total, chunk):
+            k = min(chunk, total - t0)
+            sp = [v[t0:t0 + k] if isinstance(v, torch.Tensor) and v.dim() == 2 else v for v in (setpoint_r, setpoint_p)]
+            controller._launch_rollout(k, sp[0], sp[1], {},
+                                       (weights[t0:t0 + k], alive, steps, failed, max_angle, g_tau, pos))
+        packed = torch.cat([steps.double().unsqueeze(1), failed.double().unsqueeze(1), max_angle.double().unsqueeze(1),
+                            g_tau.unsqueeze(1), pos.double()], 1).cpu().numpy()  # the one host read
+        return {"steps": packed[:, 0].astype(np.int64), "failed": packed[:, 1] != 0,
+                "max_angle_deg": packed[:, 2].astype(np.float32), "G_tau": packed[:, 3],
+                "pos2d": packed[:, 4:6].astype(np.float32)}
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     steps = torch.zeros(n, dtype=torch.int64, device=dev)
     failed = torch.zeros(n, dtype=torch.bool, device=dev)

@@ -490,6 +490,24 @@ class BallbotVecEnv:
         if args.buf_terminal_obs and args.buf_flags:
             self._record(C.c_void_p(args.buf_terminal_obs), C.c_void_p(args.buf_flags), int(args.n_steps))
 
+    def run_pid_rollout(self, args) -> None:
+        """K steps of the PID balance loop in one launch (bb_pid_rollout; args: _native.PIDRolloutArgs
+        filled by BatchedPID.rollout / balance).  Built-in rewards only; the cameras are not rendered."""
+        if self.cameras:
+            raise RuntimeError("bb_pid_rollout does not render the cameras; act() and step() do")
+        if self._host_reward is not None:
+            raise RuntimeError("bb_pid_rollout needs a built-in reward (a host plugin runs per step())")
+        if self._reward_error:
+            raise ValueError(self._reward_error)
+        if "bb_pid_rollout" not in N.EXPORTS:
+            raise RuntimeError("this build has no bb_pid_rollout")
+        if self._log_on and self._log_recording and not (args.buf_terminal_obs and args.buf_flags):
+            raise RuntimeError("this env records per-episode logs (log_options): the PID rollout needs "
+                               "buf_terminal_obs and buf_flags ([K][n][15] float32, [K][n] uint8)")
+        N.check(N.lib().bb_pid_rollout(self._h, C.byref(args), int(self.auto_reset), self._stream()), "bb_pid_rollout")
+        if args.buf_terminal_obs and args.buf_flags:
+            self._record(C.c_void_p(args.buf_terminal_obs), C.c_void_p(args.buf_flags), int(args.n_steps))
+
     def step_async_raw(self, actions: torch.Tensor, full_outputs: bool = False) -> None:
         """Launch-only step (graph capture / benchmarking): no derived tensors;
         full_outputs: also the terminal obs and pos2d buffers (an env that logs always

@@ -939,6 +939,184 @@ __global__ __launch_bounds__(64) void rollout_kernel(ModelT<T> mg, EnvCfg cfg, D
   }
 }
 
+// bb_pid_rollout's arguments on the device (bb_pid_rollout_args, field for field)
+struct PidRolloutDev {
+  PidCfg cfg;
+  int K;
+  const float* sp;         // [n][2] or NULL
+  const float* sp_seq;     // [K][n][2] or NULL
+  float* state;            // [n][4] in/out
+  float* obs;              // [n][15] in/out
+  uint8_t* done;           // [n] in/out
+  float* rew;              // [n] or NULL: the last step's
+  float* tobs;             // [n][15] or NULL
+  float* pos2d;            // [n][2] or NULL
+  float* b_act;            // traces, each [K][n][..] or NULL
+  float* b_deg;
+  float* b_obs;
+  float* b_rew;
+  uint8_t* b_flags;
+  float* b_tobs;
+  float* b_p2;
+  const double* weights;   // [K]; NULL: no summary
+  uint8_t* alive;          // balance()'s accumulators, [n] in/out
+  long long* steps;
+  uint8_t* failed;
+  float* max_angle;
+  double* g_tau;
+  float* sum_pos2d;        // [n][2]
+};
+
+// What pid_rollout_kernel carries from step to step for one env, in static LDS: held in registers
+// across the step it cost the launch without the full step 27 spilled VGPRs (fp64) where
+// multi_step_kernel has 8; here the step keeps multi_step_kernel's registers, and a parked step
+// leaves the carry as it was without anything to restore.  120 B per team.
+struct PidCarry {
+  float o[15];    // the observation the next action is computed from
+  float st[4];    // the controller row
+  int prev;       // the flags of the step before
+  PidSummary sm;  // balance()'s accumulators (with a summary attached)
+};
+
+// K steps of the PID balance loop (bb_pid_rollout) in ONE launch: every env runs its K steps of
+// (controller, env step, balance()'s accumulation) back to back on its team, as rollout_kernel
+// runs the PPO policy -- the controller reads nothing but its own env.  Per step: clear the
+// controller row if the step before terminated (BatchedPID's binding to env.done), pid_row
+// (bb_pid.h, bb_pid_act's very function) on the carried observation, then team_step with the
+// unclipped commands.  Every lane of the team runs pid_row on the same values (broadcast LDS
+// reads of the carry), so the commands are team-uniform and the same bits as one lane would give.
+// The step's terminal observation and pos2d go through the env's LDS scratch (EnvWork::g, free
+// outside a step): team_step's lead stores them there and reads them back for the traces, the
+// env's own buffers (the last step) and the summary.
+// Two launches (park != NULL), as rollout_kernel: HO = false parks an env at the step the fast
+// path hands over, with everything the loop carries (PidCarry) as before that step -- the carry is
+// only written after a step that was taken -- and it goes back to the in/out argument buffers,
+// which the HO = true launch resumes from at park[e].  The action / angle rows a parked step
+// wrote are rewritten identically.
+template <typename T, bool HO>
+__global__ __launch_bounds__(64) void pid_rollout_kernel(ModelT<T> mg, EnvCfg cfg, Dev d, PidRolloutDev pr,
+                                                         int auto_reset, int L, int epw, int* __restrict__ park) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int nwg = int(gridDim.x), b = int(blockIdx.x);
+  const int g = (nwg & 7) ? b : (b & 7) * (nwg >> 3) + (b >> 3);  // XCD-aware order, as step_kernel
+  __shared__ ModelStage<T> ms;
+  if (threadIdx.x == 0) stage_model(ms, mg);
+  __syncthreads();
+  const ModelT<T>& m = ms.m;
+  const Team tm{L, int(threadIdx.x) & (L - 1)};
+  const int team = threadIdx.x / L;
+  if (team >= epw) return;
+  const int e = g * epw + team;
+  if (unsigned(e) >= unsigned(d.n)) return;
+  const int K = pr.K;
+  int t0 = 0;
+  if (HO && park) {  // the finish launch: only parked envs, from their parked step
+    t0 = park[e];
+    if (t0 >= K) return;  // team-uniform
+  }
+  const bool lead = tm.tl == 0;
+  EnvWork<T>& W = team_work<T>(smem, team);
+  T* bk = reinterpret_cast<T*>(smem + size_t(epw) * work_stride<T>()) + team * (NQ + 2 * NV);
+  static_assert(sizeof(W.g) >= 17 * sizeof(float), "terminal obs + pos2d must fit in EnvWork::g");
+  float* lt = reinterpret_cast<float*>(W.g);  // [0..14] terminal obs, [15..16] pos2d (the lead's)
+  __shared__ unsigned s_cnt[WAVE / TEAM][8];
+  __shared__ PidCarry s_carry[WAVE / TEAM];
+  unsigned* cnt = s_cnt[team];
+  PidCarry& c = s_carry[team];
+  const size_t n = size_t(d.n), se = size_t(e);
+  const bool summary = pr.weights != nullptr;
+  if (lead) {
+    W.bspill = body_spill_of<T>(d, e);
+    counts_clear(cnt);
+#pragma unroll
+    for (int i = 0; i < 15; i++) c.o[i] = pr.obs[15 * se + i];
+#pragma unroll
+    for (int i = 0; i < 4; i++) c.st[i] = pr.state[4 * se + i];
+    c.prev = pr.done[e];
+    if (summary) {
+      c.sm.alive = pr.alive[e]; c.sm.failed = pr.failed[e]; c.sm.steps = pr.steps[e];
+      c.sm.max_angle = pr.max_angle[e]; c.sm.g_tau = pr.g_tau[e];
+      c.sm.pos[0] = pr.sum_pos2d[2 * se]; c.sm.pos[1] = pr.sum_pos2d[2 * se + 1];
+    }
+  }
+  T* q = W.qn;
+  T* v = W.vn;
+  T* w = W.wn;
+  int step;
+  load_state(d, e, q, v, w, step);
+  int tid = d.terrain[e];
+  int parked = K;
+#pragma unroll 1
+  for (int t = t0; t < K; t++) {
+    const size_t row = size_t(t) * n + se;
+    const float* sp = pr.sp_seq ? pr.sp_seq + 2 * row : (pr.sp ? pr.sp + 2 * se : nullptr);
+    team_sync();  // the lead's carry of the step before (or of the launch's start)
+    float a[3], deg, st[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) st[i] = c.st[i];
+    pid_row(pr.cfg, c.o + 9, sp, (c.prev & BB_DONE_TERMINATED) != 0, st, a, &deg);
+    if (lead) {
+      if (pr.b_act) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) pr.b_act[3 * row + j] = a[j];
+      }
+      if (pr.b_deg) pr.b_deg[row] = deg;
+    }
+    float o[15], r;
+    // FUSE in the launch that has only the fast step compiled in, as multi_step_kernel
+    const int fl = team_step<T, HO, false, !HO>(m, cfg, d, e, tid, q, v, w, step, bk, a, W, o, r, lt, lt + 15,
+                                                auto_reset, tm, cnt);
+    if (!HO && (fl & F_PARKED)) {  // team-uniform: the env resumes at step t in the finish launch
+      parked = t;
+      break;
+    }
+    if (lead) {
+      const float p2[2] = {lt[15], lt[16]};
+#pragma unroll
+      for (int i = 0; i < 15; i++) c.o[i] = o[i];
+#pragma unroll
+      for (int i = 0; i < 4; i++) c.st[i] = st[i];
+      c.prev = fl & 0xFF;
+      if (pr.b_obs) {
+#pragma unroll
+        for (int i = 0; i < 15; i++) pr.b_obs[15 * row + i] = o[i];
+      }
+      if (pr.b_rew) pr.b_rew[row] = r;
+      if (pr.b_flags) pr.b_flags[row] = uint8_t(fl);
+      if (pr.b_tobs) {
+#pragma unroll
+        for (int i = 0; i < 15; i++) pr.b_tobs[15 * row + i] = lt[i];
+      }
+      if (pr.b_p2) { pr.b_p2[2 * row] = p2[0]; pr.b_p2[2 * row + 1] = p2[1]; }
+      if (t == K - 1) {  // what the K-th bb_step leaves in the env's own buffers
+        if (pr.rew) pr.rew[e] = r;
+        if (pr.tobs) {
+#pragma unroll
+          for (int i = 0; i < 15; i++) pr.tobs[15 * se + i] = lt[i];
+        }
+        if (pr.pos2d) { pr.pos2d[2 * se] = p2[0]; pr.pos2d[2 * se + 1] = p2[1]; }
+      }
+      if (summary) pid_summary_step(c.sm, deg, r, fl, p2, pr.weights[t]);
+    }
+  }
+  team_sync();
+  if (lead) {
+    store_state(d, e, q, v, w, step);
+    counts_flush(d, cnt);
+    if (!HO) park[e] = parked;
+#pragma unroll
+    for (int i = 0; i < 15; i++) pr.obs[15 * se + i] = c.o[i];
+#pragma unroll
+    for (int i = 0; i < 4; i++) pr.state[4 * se + i] = c.st[i];
+    pr.done[e] = uint8_t(c.prev);
+    if (summary) {
+      pr.alive[e] = c.sm.alive; pr.failed[e] = c.sm.failed; pr.steps[e] = c.sm.steps;
+      pr.max_angle[e] = c.sm.max_angle; pr.g_tau[e] = c.sm.g_tau;
+      pr.sum_pos2d[2 * se] = c.sm.pos[0]; pr.sum_pos2d[2 * se + 1] = c.sm.pos[1];
+    }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(64) void reset_kernel(ModelT<T> m, Dev d, const uint8_t* mask, float* obs) {
   const int e = blockIdx.x * WAVE + threadIdx.x;
@@ -2081,6 +2259,27 @@ int launch_rollout(bb_handle* h, const RolloutDev& ro, hipStream_t s) {
   return 0;
 }
 
+// bb_pid_rollout: pid_rollout_kernel in rollout_kernel's serial forms on every bank (two launches
+// with the hand-overs parked, or one with them inline); a controller inside the relief pair or
+// the work queue is not built
+template <typename T>
+int launch_pid_rollout(bb_handle* h, const PidRolloutDev& pr, int ar, hipStream_t s) {
+  const int epw = h->epw;
+  const int blocks = (h->n + epw - 1) / epw;
+  const size_t lds = rollout_lds_bytes<T>(epw);
+  if (h->multi_park) {
+    hipLaunchKernelGGL((pid_rollout_kernel<T, false>), dim3(blocks), dim3(WAVE), lds, s, model_of<T>(h), h->cfg, h->d,
+                       pr, ar, h->team, epw, h->d.park);
+    hipLaunchKernelGGL((pid_rollout_kernel<T, true>), dim3(blocks), dim3(WAVE), lds, s, model_of<T>(h), h->cfg, h->d,
+                       pr, ar, h->team, epw, h->d.park);
+  } else {
+    hipLaunchKernelGGL((pid_rollout_kernel<T, true>), dim3(blocks), dim3(WAVE), lds, s, model_of<T>(h), h->cfg, h->d,
+                       pr, ar, h->team, epw, (int*)nullptr);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // the relief pair on relief banks (see relief_pair_kernel): routes, rings, the
 // two persistent launches on the caller's stream and the handle's side stream,
 // then the split adaptation.  gate: the adaptive route's flag (NULL: always run)
@@ -2166,6 +2365,37 @@ extern "C" __attribute__((visibility("hidden"))) int bb_pair_launch_tu(bb_handle
 }
 #endif
 
+// pid_rollout_kernel and its launch are compiled in a translation unit of their own as well,
+// bb_pid_rollout.hip (this file with BB_PID_TU, the product's flags): instantiated beside the
+// other kernels they changed the register allocation of multi_step_kernel<double, false> (same
+// registers, LDS and occupancy, 8 bytes less code) and bb_step_multi measured 0.2% slower; in
+// their own unit every kernel of this one is the code it was.  (internal to the library: hidden,
+// not part of the C-ABI; pr: a PidRolloutDev.)
+extern "C" __attribute__((visibility("hidden"))) int bb_pid_rollout_launch_tu(bb_handle* h, int fp64, const void* pr,
+                                                                             int ar, hipStream_t s);
+// once per handle: the kernels' dynamic-LDS limit -> a hipError_t
+extern "C" __attribute__((visibility("hidden"))) int bb_pid_rollout_setup_tu(int fp64, int epw);
+#ifdef BB_PID_TU
+template <typename T>
+int pid_rollout_setup(int epw) {
+  const int lb = int(rollout_lds_bytes<T>(epw));
+  const void* ks[2] = {(const void*)pid_rollout_kernel<T, false>, (const void*)pid_rollout_kernel<T, true>};
+  for (const void* k : ks) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lb);
+    if (e != hipSuccess) return int(e);
+  }
+  return 0;
+}
+extern "C" __attribute__((visibility("hidden"))) int bb_pid_rollout_setup_tu(int fp64, int epw) {
+  return fp64 ? pid_rollout_setup<double>(epw) : pid_rollout_setup<float>(epw);
+}
+extern "C" __attribute__((visibility("hidden"))) int bb_pid_rollout_launch_tu(bb_handle* h, int fp64, const void* pr,
+                                                                             int ar, hipStream_t s) {
+  const PidRolloutDev& p = *static_cast<const PidRolloutDev*>(pr);
+  return fp64 ? launch_pid_rollout<double>(h, p, ar, s) : launch_pid_rollout<float>(h, p, ar, s);
+}
+#endif
+
 namespace {
 
 template <typename T>
@@ -2235,7 +2465,7 @@ int launch_multi(bb_handle* h, const float* a, int K, float* o, float* r, uint8_
 }
 }  // namespace
 
-#ifndef BB_PAIR_TU
+#if !defined(BB_PAIR_TU) && !defined(BB_PID_TU)
 extern "C" {
 
 int bb_abi_version(void) { return BB_ABI_VERSION; }
@@ -2482,6 +2712,8 @@ int bb_create(int n_envs, int device, const bb_params* p, bb_handle** out) {
                          h->fp64 ? (const void*)rollout_kernel<double, true, RolloutLog>
                                  : (const void*)rollout_kernel<float, true, RolloutLog>};
     for (const void* k : rk) HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, rlb));
+    // (pid_rollout_kernel gets its limit in its own unit: bb_pid_rollout_setup_tu)
+    HIPCHK((hipError_t)bb_pid_rollout_setup_tu(h->fp64, h->epw));
     const int qlb = (int)(h->fp64 ? relief_lds_bytes<double>() : relief_lds_bytes<float>());
     const void* qk[3] = {h->fp64 ? (const void*)relief_multi_kernel<double, false>
                                  : (const void*)relief_multi_kernel<float, false>,
@@ -2960,6 +3192,44 @@ int bb_pid_act(const bb_pid_cfg* cfg, const float* orient, int64_t orient_stride
   return 0;
 }
 
+int bb_pid_rollout(bb_handle* h, const bb_pid_rollout_args* a, int auto_reset, void* stream) {
+  // argument checks first (none of them touches the handle or HIP)
+  if (!h) return fail("bb_pid_rollout: NULL handle");
+  if (!a) return fail("bb_pid_rollout: NULL args");
+  if (a->n_steps < 1) return fail("bb_pid_rollout: n_steps must be >= 1 (got %d)", a->n_steps);
+  if (!(a->cfg.dt > 0.f)) return fail("bb_pid_rollout: dt must be > 0 (got %g)", (double)a->cfg.dt);
+  if (!(a->cfg.limit > 0.f)) return fail("bb_pid_rollout: limit must be > 0 (got %g)", (double)a->cfg.limit);
+  if (a->cfg.orient_kind != BB_PID_ROTVEC)
+    return fail("bb_pid_rollout: orient_kind must be BB_PID_ROTVEC (0): the controller reads the observation's "
+                "rotation vector (got %d)", a->cfg.orient_kind);
+  if (a->cfg.space != BB_PID_MOTOR)
+    return fail("bb_pid_rollout: space must be BB_PID_MOTOR (0): the env steps on motor commands (got %d)",
+                a->cfg.space);
+  if (a->setpoint && a->setpoint_seq)
+    return fail("bb_pid_rollout: setpoint and setpoint_seq are both set (at most one of the two)");
+  {
+    const int set = !!a->weights + !!a->alive + !!a->steps + !!a->failed + !!a->max_angle + !!a->g_tau + !!a->sum_pos2d;
+    if (set != 0 && set != 7)
+      return fail("bb_pid_rollout: the summary is partly set (%d of 7 pointers): weights, alive, steps, failed, "
+                  "max_angle, g_tau and sum_pos2d go together (all, or all NULL)", set);
+  }
+  if (!a->state || !a->obs || !a->done) return fail("bb_pid_rollout: state/obs/done must be non-NULL");
+  if (*h->fault_host) return faulted(h, "bb_pid_rollout");
+  if (h->cfg.reward_kind == BB_REWARD_NONE)
+    return fail("bb_pid_rollout: the reward is a host-side plugin (BB_REWARD_NONE); step with bb_step instead");
+  PidRolloutDev pr;
+  pr.cfg = PidCfg{a->cfg.dt, a->cfg.k_p, a->cfg.k_i, a->cfg.k_d, a->cfg.limit, a->cfg.orient_kind, a->cfg.space};
+  pr.K = a->n_steps; pr.sp = a->setpoint; pr.sp_seq = a->setpoint_seq; pr.state = a->state; pr.obs = a->obs;
+  pr.done = a->done; pr.rew = a->reward; pr.tobs = a->terminal_obs; pr.pos2d = a->pos2d; pr.b_act = a->buf_actions;
+  pr.b_deg = a->buf_angle_deg; pr.b_obs = a->buf_obs; pr.b_rew = a->buf_reward; pr.b_flags = a->buf_flags;
+  pr.b_tobs = a->buf_terminal_obs; pr.b_p2 = a->buf_pos2d; pr.weights = a->weights; pr.alive = a->alive;
+  pr.steps = reinterpret_cast<long long*>(a->steps); pr.failed = a->failed; pr.max_angle = a->max_angle;
+  pr.g_tau = a->g_tau; pr.sum_pos2d = a->sum_pos2d;
+  if (bb_pid_rollout_launch_tu(h, h->fp64, &pr, auto_reset, (hipStream_t)stream))
+    return fail("bb_pid_rollout: launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
 int bb_get_state(bb_handle* h, double* qpos, double* qvel, double* warm, int32_t* steps) {
   if (!h) return fail("bb_get_state: NULL handle");
   HIPCHK(hipSetDevice(h->device));
@@ -3259,4 +3529,4 @@ int bb_get_offsets(bb_handle* h, float* out) {
 }
 
 }  // extern "C"
-#endif  // BB_PAIR_TU
+#endif  // BB_PAIR_TU, BB_PID_TU

@@ -19,6 +19,14 @@
 #else
 #define BB_PID_HD inline
 #endif
+// The double-precision angle code below is compiled for the GPU under bb_pid.hip's contraction mode
+// (the compiler's default) in every unit that inlines it, whatever file-level pragma that unit sets
+// (bb_kernels.hip: contract(on)), so that pid_rollout_kernel's angles are bb_pid_act's bit for bit.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BB_PID_DEVICE_CONTRACT _Pragma("clang fp contract(fast)")
+#else
+#define BB_PID_DEVICE_CONTRACT
+#endif
 
 namespace bb {
 
@@ -35,6 +43,7 @@ struct PidCfg {
 // o[0..2], R = I + sin(th) K + (1 - cos(th)) K^2 with identity below 1e-14 rad.  Scalar reads only:
 // a row inside an observation is float-aligned.
 BB_PID_HD void pid_third_row(const float* o, int kind, float r[3]) {
+  BB_PID_DEVICE_CONTRACT
   if (kind == PID_ROTMAT) {
     r[0] = o[6]; r[1] = o[7]; r[2] = o[8];
     return;
@@ -60,6 +69,7 @@ BB_PID_HD void pid_third_row(const float* o, int kind, float r[3]) {
 // clamp written with comparisons passes it on, as torch.clamp does).
 BB_PID_HD void pid_row(const PidCfg& cfg, const float* orient, const float* sp, bool clear, float* st, float* out,
                        float* angle_deg) {
+  BB_PID_DEVICE_CONTRACT
   float r[3];
   pid_third_row(orient, cfg.orient_kind, r);
   const double r0 = r[0], r1 = r[1], r2 = r[2];
@@ -97,6 +107,39 @@ BB_PID_HD void pid_row(const PidCfg& cfg, const float* orient, const float* sp, 
       out[k] = c < -cfg.limit ? -cfg.limit : (c > cfg.limit ? cfg.limit : c);
     }
   }
+}
+
+// balance()'s per-env accumulators (controllers/pid.py: balance, the loop of the reference's
+// scripts/test_pid.py:38-65), one env's row of bb_pid_rollout's summary buffers
+struct PidSummary {
+  uint8_t alive, failed;  // 0 / 1
+  int64_t steps;
+  float max_angle;
+  double g_tau;
+  float pos[2];
+};
+
+// One step of balance()'s accumulation for one env, in its order: deg is the tilt the controller saw
+// before the step, r / flags / p2 the step's reward, BB_DONE_* bits and base position, w = gamma^t
+// (from the host: no pow here, so G_tau does not depend on a device's pow).  max_angle follows
+// torch.maximum (a NaN propagates); the product and the sum of G_tau are two roundings, never one
+// fused multiply-add.
+BB_PID_HD void pid_summary_step(PidSummary& s, float deg, float r, int flags, const float* p2, double w) {
+  const bool alive = s.alive != 0, term = (flags & 1) != 0, failure = (flags & 2) != 0;  // BB_DONE_TERMINATED, _FAILURE
+  if (alive) s.max_angle = deg != deg ? deg : (s.max_angle != s.max_angle || s.max_angle > deg ? s.max_angle : deg);
+  s.steps += alive;
+  {
+    // the product rounded, then the sum rounded, as torch's separate mul and add kernels.  Written as
+    // plain operators under contract(off) on the host and the device alike: HIP's __dmul_rn /
+    // __dadd_rn are the plain operators too, and written with them the device build still fused the
+    // two into one v_fma_f64 (1 ulp off in G_tau after 120 steps, measured against balance()).
+#pragma clang fp contract(off)
+    const double prod = double(r) * w;
+    s.g_tau = s.g_tau + (alive ? prod : 0.0);
+  }
+  if (alive) { s.pos[0] = p2[0]; s.pos[1] = p2[1]; }
+  s.failed |= uint8_t(alive && term && failure);
+  s.alive = uint8_t(alive && !term);
 }
 
 #if defined(__HIPCC__)

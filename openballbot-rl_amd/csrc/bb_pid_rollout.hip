@@ -1,0 +1,9 @@
+// bb_pid_rollout.hip -- pid_rollout_kernel and its launch (bb_pid_rollout) as their own
+// translation unit: bb_kernels.hip compiled with BB_PID_TU (everything but the C-ABI), with the
+// product's flags, so that the kernels of bb_kernels.hip's own unit are compiled exactly as they
+// were before this kernel existed (see bb_pid_rollout_launch_tu in bb_kernels.hip).
+#define BB_PID_TU
+#ifdef BB_PHASE_CLOCKS  // diagnostic builds: this unit's counters under their own name
+#define bb_phase_cycles bb_phase_cycles_pid
+#endif
+#include "bb_kernels.hip"
