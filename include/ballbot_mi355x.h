@@ -29,6 +29,7 @@
  *   bb_reward_terms  reward_term_1_hist / reward_term_2_hist of _save_logs  ballbot_env.py:929-937, 673-699
  *   bb_pid_act       PID.act, the balance controller             controllers/pid.py:61-101
  *   bb_pid_rollout   the install check's loop (PID.act + env.step) in one launch   scripts/test_pid.py:38-65
+ *   bb_eval_track    SB3 evaluate_policy's episode accounting (EvalCallback) + the policy's per-step staging
  *   bb_depth_encoder frozen rgbd encoder of the camera policy, fused
  *   bb_gae           SB3 RolloutBuffer.compute_returns_and_advantage (PPO)
  *   bb_forward       mujoco.mj_forward (diagnostic)             ballbot_env.py:525,620
@@ -452,7 +453,13 @@ int bb_rollout_track(const float* reward_dev, const uint8_t* flags_dev, int done
  * Writes features row i at out_dev + i * out_stride (20 floats).  The pointers
  * in bb_encoder_params are the module's device tensors (running statistics and
  * counters are written in train mode; counters may be NULL).  Six launches on
- * stream; graph-capturable. */
+ * stream; graph-capturable.
+ * A negative index_dev[i] in eval mode skips row i: no image is read for it and its out row is
+ * left as it was (the workspace is scratch either way), so an index of the rows whose cameras
+ * re-rendered (bb_eval_track's fresh) refreshes cached features in place with no host count.  In
+ * train mode a negative entry is an error (batch statistics need every row): outside a stream
+ * capture the index is read back and checked (a wait for the stream); inside a capture the check
+ * cannot run and non-negative entries are the caller's contract. */
 typedef struct bb_encoder_params {
   const float *conv1_w, *conv1_b, *bn1_w, *bn1_b;
   float *bn1_mean, *bn1_var;
@@ -468,6 +475,46 @@ int bb_depth_encoder_workspace_bytes(int64_t n, int64_t* bytes);
 int bb_depth_encoder(const bb_encoder_params* params, const float* images_dev, int64_t image_stride,
                      const int64_t* index_dev, int64_t n, int height, int width, int train, float momentum, float eps,
                      float* out_dev, int64_t out_stride, float* workspace_dev, int64_t workspace_bytes, void* stream);
+/* One evaluation step's bookkeeping on the device (SB3 evaluate_policy over a Monitor-wrapped
+ * VecEnv, as the reference's EvalCallback calls it, ballbot_rl/training/callbacks.py:607-617): the
+ * episode accounting, and the per-step staging of the policy's input.  No handle.
+ * Accounting (flags != NULL), per env e: ep_ret[e] += (double)reward[e], ep_len[e] += 1; an env
+ * whose flags carry BB_DONE_TERMINATED finishes an episode: while counts[e] < targets[e] it is
+ * listed (counts[e] goes up, book[1] down), otherwise dropped; its sums are cleared either way.
+ * The episodes of one call are listed in env order after those of every earlier call -- the row
+ * order of evaluations.npz: row book[0] + rank of tab_ret (float64 return, not rounded), tab_len,
+ * tab_env and tab_step (the number of steps tracked when it ended, 1 for the first call).
+ * book int64[4] = {episodes listed, episodes still wanted, steps tracked, overflow}: the caller
+ * zeroes it and sets book[1] = sum(targets) before the first call; a listing at or past cap is
+ * counted (book[0], book[1]) but not written, and sets book[3] = 1.  flags == NULL is the priming
+ * call after a reset: staging only.
+ * Staging (either output may be NULL; both need obs): feats float[n][56] gets columns 0:12 =
+ * obs[0:12], column 12 = rel_ts, columns 53:56 = obs[12:15]; columns 13:53 (the camera features)
+ * are not touched.  fresh int64[n] gets e where rel_ts[e] == 0 (the env's cameras rendered in this
+ * step), else -1: bb_depth_encoder's index.  rel_ts == NULL (no cameras): column 12 is left alone
+ * and fresh is all -1.
+ * One launch on stream (workgroup 0 accounts, the others stage 1024 envs each), kernel node only:
+ * no memset, no allocation, no atomics, no host read; graph-capturable.  Any n >= 1.  (ABI 21
+ * still holds: purely additive, detected by symbol.) */
+typedef struct bb_eval_args {
+  int32_t n, cap;           /* envs; rows of the episode table */
+  const float* reward;      /* [n] */
+  const uint8_t* flags;     /* [n] BB_DONE_* bits of the step, or NULL (priming) */
+  const float* obs;         /* [n][15] after the step and any auto-reset */
+  const float* rel_ts;      /* [n] or NULL */
+  const int32_t* targets;   /* [n] episodes each env owes */
+  double* ep_ret;           /* [n] in/out */
+  int64_t* ep_len;          /* [n] in/out */
+  int32_t* counts;          /* [n] in/out: episodes listed per env */
+  double* tab_ret;          /* [cap] */
+  int64_t* tab_len;         /* [cap] */
+  int32_t* tab_env;         /* [cap] */
+  int64_t* tab_step;        /* [cap] */
+  int64_t* book;            /* [4] in/out */
+  float* feats;             /* [n][56] or NULL */
+  int64_t* fresh;           /* [n] or NULL */
+} bb_eval_args;
+int bb_eval_track(const bb_eval_args* args, void* stream);
 /* copy terrain bank slot terrain_id (float32[293*293]) to host memory */
 int bb_get_hfield(bb_handle* h, int terrain_id, float* data_host);
 /* pin per-env terrain ids (device int32[n]) for every later reset; an id

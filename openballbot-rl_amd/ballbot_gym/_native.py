@@ -133,6 +133,13 @@ class PIDRolloutArgs(C.Structure):
                                         "pos2d") + PID_ROLLOUT_TRACES + PID_ROLLOUT_SUMMARY]
 
 
+class EvalArgs(C.Structure):
+    """bb_eval_args (include/ballbot_mi355x.h): one evaluation step's accounting and staging."""
+    _fields_ = [("n", C.c_int32), ("cap", C.c_int32)] + [
+        (name, C.c_void_p) for name in ("reward", "flags", "obs", "rel_ts", "targets", "ep_ret", "ep_len", "counts",
+                                        "tab_ret", "tab_len", "tab_env", "tab_step", "book", "feats", "fresh")]
+
+
 ENCODER_FIELDS = ("conv1_w", "conv1_b", "bn1_w", "bn1_b", "bn1_mean", "bn1_var", "bn1_count",
                   "conv2_w", "conv2_b", "bn2_w", "bn2_b", "bn2_mean", "bn2_var", "bn2_count",
                   "fc_w", "fc_b", "bn3_w", "bn3_b", "bn3_mean", "bn3_var", "bn3_count")
@@ -152,7 +159,7 @@ EXPORTS = [
     "bb_set_terrain_stream", "bb_get_env_terrain", "bb_kernel_times", "bb_step_multi", "bb_rollout",
     "bb_set_terrain_rng", "bb_get_terrain_rng", "bb_pair_counters", "bb_pair_env_times", "bb_check",
     "bb_reward_terms", "bb_default_view", "bb_render_view", "bb_render_rgbd", "bb_pid_act",
-    "bb_pid_rollout",
+    "bb_pid_rollout", "bb_eval_track",
 ]
 
 ABI_VERSION = 21  # include/ballbot_mi355x.h BB_ABI_VERSION
@@ -162,7 +169,7 @@ _lib = None
 
 HIP_SOURCES = ("bb_kernels.hip", "bb_pair.hip", "bb_terrain.hip", "bb_rollout.hip", "bb_render.hip", "bb_view.hip",
                "bb_rgbd.hip", "bb_ppo.hip", "bb_mlp.hip", "bb_encoder.hip", "bb_episode_log.hip", "bb_pid.hip",
-               "bb_pid_rollout.hip")
+               "bb_pid_rollout.hip", "bb_eval.hip")
 # per-source flags: the relief pair's unit without MachineLICM (bb_kernels.hip: bb_pair_launch_tu)
 SOURCE_FLAGS = {"bb_pair.hip": ["-mllvm", "-disable-machine-licm"]}
 
@@ -278,6 +285,7 @@ def _load(path: Path):
                                  vp]
     L.bb_pid_act.argtypes = [C.POINTER(PIDCfg), vp, C.c_int64, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
     L.bb_pid_rollout.argtypes = [vp, C.POINTER(PIDRolloutArgs), C.c_int, vp]
+    L.bb_eval_track.argtypes = [C.POINTER(EvalArgs), vp]
     L.bb_rollout_track.argtypes = [vp, vp, C.c_int, C.c_int] + [vp] * 8
     L.bb_depth_encoder_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_int64)]
     L.bb_depth_encoder.argtypes = [C.POINTER(EncoderParams), vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int,

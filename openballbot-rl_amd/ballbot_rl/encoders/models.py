@@ -92,13 +92,21 @@ def fusable_encoder(enc: nn.Module) -> bool:
     return conv_ok and shapes_ok and bn_ok and act_ok and frozen and dtypes
 
 
-def fused_encoder_forward(enc: nn.Sequential, x: torch.Tensor, index: "torch.Tensor | None" = None) -> torch.Tensor:
+def fused_encoder_forward(enc: nn.Sequential, x: torch.Tensor, index: "torch.Tensor | None" = None,
+                          out: "torch.Tensor | None" = None, out_stride: "int | None" = None,
+                          workspace: "torch.Tensor | None" = None) -> torch.Tensor:
     """bb_depth_encoder on x [n, 1, 64, 64] (cuda, fp32; a channel slice of the
     [n, 2, 64, 64] camera tensor is fine): the frozen encoder's output [n, 20] with
     torch's BatchNorm semantics for enc.training (train: batch statistics and a
     running-statistics update; eval: running statistics).  No autograd graph.
     index (int64 [m], on the device): encode rows index[i] of x instead (a
-    minibatch gathered inside the kernel); the output has m rows."""
+    minibatch gathered inside the kernel); the output has m rows.  In eval mode a
+    negative index[i] skips row i: nothing is read and its output row keeps what it held.
+    out / out_stride: write row i at out.data_ptr() + 4 i out_stride bytes instead of
+    allocating (out: fp32 on x's device, e.g. a column slice feats[:, 13:33] of a [n, 56]
+    buffer with out_stride 56; default stride: out.stride(0)); `out` is returned.
+    workspace: a caller-owned fp32 scratch of at least bb_depth_encoder_workspace_bytes(m)
+    bytes (a captured graph must own it); default: allocated per call."""
     import ctypes as C
 
     from ballbot_gym import _native as N
@@ -118,11 +126,28 @@ def fused_encoder_forward(enc: nn.Sequential, x: torch.Tensor, index: "torch.Ten
     nbytes = C.c_int64()
     L = N.lib()
     N.check(L.bb_depth_encoder_workspace_bytes(int(n), C.byref(nbytes)), "bb_depth_encoder_workspace_bytes")
-    ws = torch.empty(int(nbytes.value) // 4 + 4, device=x.device)
-    out = torch.empty(n, 20, device=x.device)
+    if workspace is None:
+        ws = torch.empty(int(nbytes.value) // 4 + 4, device=x.device)
+    else:
+        ws = workspace
+        if ws.dtype != torch.float32 or ws.device != x.device or not ws.is_contiguous() \
+                or ws.numel() * 4 < int(nbytes.value):
+            raise ValueError(f"fused_encoder_forward: workspace must be a contiguous fp32 tensor of >= "
+                             f"{int(nbytes.value)} bytes on {x.device}")
+    if out is None:
+        if out_stride is not None:
+            raise ValueError("fused_encoder_forward: out_stride needs out")
+        out = torch.empty(n, 20, device=x.device)
+        stride = 20
+    else:
+        stride = int(out.stride(0) if out_stride is None else out_stride)
+        if out.dtype != torch.float32 or out.device != x.device or out.dim() != 2 or out.shape[0] < n \
+                or out.shape[1] < 20 or out.stride(1) != 1 or stride < 20 or (n > 1 and stride != out.stride(0)):
+            raise ValueError("fused_encoder_forward: out must be an fp32 [>= n, >= 20] tensor on the images' device "
+                             "with unit column stride, and out_stride its row stride (>= 20)")
     stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
     N.check(L.bb_depth_encoder(C.byref(p), C.c_void_p(x.data_ptr()), int(x.stride(0)),
                                None if index is None else C.c_void_p(index.data_ptr()), int(n), 64, 64,
                                int(bool(enc.training)), float(b1.momentum), float(b1.eps), C.c_void_p(out.data_ptr()),
-                               20, C.c_void_p(ws.data_ptr()), int(nbytes.value), stream), "bb_depth_encoder")
+                               stride, C.c_void_p(ws.data_ptr()), int(nbytes.value), stream), "bb_depth_encoder")
     return out

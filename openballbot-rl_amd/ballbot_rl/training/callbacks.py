@@ -32,8 +32,13 @@ import numpy as np
 class EvalCallback:
     def __init__(self, eval_env, n_eval_episodes: int = 8, eval_freq: int = 5000, n_total_envs: int = 1,
                  log_path: Optional[Path] = None, best_model_save_path: Optional[Path] = None,
-                 deterministic: bool = True, callback_on_new_best=None, callback_after_eval=None):
+                 deterministic: bool = True, callback_on_new_best=None, callback_after_eval=None,
+                 fused: bool = False):
         self.eval_env = eval_env
+        # fused: the device-side evaluator (one captured graph per step, kept across evaluations;
+        # poll = 1, so every evaluation leaves the eval env where the eager loop would)
+        self.fused = bool(fused)
+        self._evaluator = None
         # called with the model: after a new best is saved / after every evaluation (None: nothing)
         self.callback_on_new_best, self.callback_after_eval = callback_on_new_best, callback_after_eval
         self.n_eval_episodes, self.eval_freq = int(n_eval_episodes), int(eval_freq)
@@ -59,8 +64,15 @@ class EvalCallback:
     def _evaluate(self, model, step: int) -> None:
         from ballbot_rl.evaluation import evaluate_policy
 
-        r = evaluate_policy(model.policy, self.eval_env, n_eval_episodes=self.n_eval_episodes,
-                            deterministic=self.deterministic)
+        if self.fused:
+            from ballbot_rl.evaluation import DeviceEvaluator
+
+            if self._evaluator is None or self._evaluator.policy is not model.policy:
+                self._evaluator = DeviceEvaluator(model.policy, self.eval_env)
+            r = self._evaluator.evaluate(self.n_eval_episodes, deterministic=self.deterministic, poll=1)
+        else:
+            r = evaluate_policy(model.policy, self.eval_env, n_eval_episodes=self.n_eval_episodes,
+                                deterministic=self.deterministic)
         ts = step * self.n_total_envs  # SB3's num_timesteps at that step
         self.timesteps.append(ts)
         self.results.append(r["episode_rewards"])

@@ -192,32 +192,15 @@ def policy_obs(obs15: torch.Tensor, depth: Optional[torch.Tensor] = None,
     return d
 
 
-def fused_mlp_slots(ppo: "BatchedPPO", update: bool = True, B: Optional[int] = None):
-    """Flat-buffer offsets of the 21 tensors bb_ppo_mlp_step reads, or None when
-    the policy/optimiser is not the reference's MLP on FlatAdamW (pi = vf =
-    [128]*4 LeakyReLU(0.01) over the 15-d proprio obs, or the 56-d features of
-    the camera policy with fused frozen encoders; 3-d action head);
-    update=True also needs a minibatch bb_ppo_mlp_step takes: B rows (default
-    ppo.batch_size; the data-parallel update passes its local batch_size / world),
-    a multiple of 256 in [256, 16384] -- else the autograd graph step runs.
-    BB_PPO_FUSED=0 disables the fused update and rollout step (A/B runs)."""
-    import os
-
-    from ballbot_rl.training.optim import FlatAdamW
-
-    if os.environ.get("BB_PPO_FUSED", "1") == "0" or ppo.device.type != "cuda":
-        return None
-    opt, pol = ppo.optimizer, ppo.policy
-    if not isinstance(opt, FlatAdamW):
-        return None
-    if update:  # the LOCAL minibatch bb_ppo_mlp_step runs: batch_size / world rows when data-parallel
-        B = int(ppo.batch_size if B is None else B)
-        if B < 256 or B % 256 or B > 16384:
-            return None
-
+def reference_mlp_tensors(pol, cameras: bool):
+    """The 21 parameter tensors bb_ppo_mlp_step / bb_ppo_mlp_act read, in their slot order (pi W0..W3,
+    pi b0..b3, vf W0..W3, vf b0..b3, action W, action b, value W, value b, log_std), or None when
+    `pol` is not the reference's MLP: pi = vf = [128]*4 LeakyReLU(0.01) over the 15-d proprio obs,
+    or (cameras) over the 56-d features of the camera policy with fused frozen encoders; 3-d action
+    head.  Needs no optimiser: a bare policy can be packed from this list (pack_mlp_params)."""
     ext = pol.features_extractor
     fd = ext.features_dim
-    if ppo.cameras:  # the camera features must come from fused frozen encoders (no trainable extractor)
+    if cameras:  # the camera features must come from fused frozen encoders (no trainable extractor)
         keys, frozen = getattr(ext, "keys", None), getattr(ext, "_frozen_keys", None)
         if keys is None or frozen is None:  # a custom extractor: the autograd path
             return None
@@ -247,8 +230,54 @@ def fused_mlp_slots(ppo: "BatchedPPO", update: bool = True, B: Optional[int] = N
         return None
     if tuple(pol.action_net.weight.shape) != (3, 128) or tuple(pol.value_net.weight.shape) != (1, 128):
         return None
-    tensors = pi + vf + [pol.action_net.weight, pol.action_net.bias, pol.value_net.weight, pol.value_net.bias,
-                         pol.log_std]
+    return pi + vf + [pol.action_net.weight, pol.action_net.bias, pol.value_net.weight, pol.value_net.bias,
+                      pol.log_std]
+
+
+def pack_mlp_params(tensors, device):
+    """A flat fp32 buffer holding copies of reference_mlp_tensors' 21 tensors, each starting on a
+    16-byte boundary (FlatAdamW's layout rule), and their 21 float offsets -> (flat, offsets).  For a
+    policy without an optimiser (evaluation); refill with refill_mlp_params after the policy moved."""
+    offsets, n = [], 0
+    for t in tensors:
+        offsets.append(n)
+        n += (t.numel() + 3) // 4 * 4
+    flat = torch.zeros(n, dtype=torch.float32, device=device)
+    refill_mlp_params(flat, offsets, tensors)
+    return flat, offsets
+
+
+@torch.no_grad()
+def refill_mlp_params(flat: torch.Tensor, offsets, tensors) -> None:
+    for t, off in zip(tensors, offsets):
+        flat[off:off + t.numel()].copy_(t.detach().reshape(-1))
+
+
+def fused_mlp_slots(ppo: "BatchedPPO", update: bool = True, B: Optional[int] = None):
+    """Flat-buffer offsets of the 21 tensors bb_ppo_mlp_step reads, or None when
+    the policy/optimiser is not the reference's MLP on FlatAdamW (pi = vf =
+    [128]*4 LeakyReLU(0.01) over the 15-d proprio obs, or the 56-d features of
+    the camera policy with fused frozen encoders; 3-d action head: reference_mlp_tensors);
+    update=True also needs a minibatch bb_ppo_mlp_step takes: B rows (default
+    ppo.batch_size; the data-parallel update passes its local batch_size / world),
+    a multiple of 256 in [256, 16384] -- else the autograd graph step runs.
+    BB_PPO_FUSED=0 disables the fused update and rollout step (A/B runs)."""
+    import os
+
+    from ballbot_rl.training.optim import FlatAdamW
+
+    if os.environ.get("BB_PPO_FUSED", "1") == "0" or ppo.device.type != "cuda":
+        return None
+    opt, pol = ppo.optimizer, ppo.policy
+    if not isinstance(opt, FlatAdamW):
+        return None
+    if update:  # the LOCAL minibatch bb_ppo_mlp_step runs: batch_size / world rows when data-parallel
+        B = int(ppo.batch_size if B is None else B)
+        if B < 256 or B % 256 or B > 16384:
+            return None
+    tensors = reference_mlp_tensors(pol, ppo.cameras)
+    if tensors is None:
+        return None
     where = {id(q): off for q, off in zip(opt.params, opt.offsets)}
     if len(opt.params) != len(tensors) or any(id(t) not in where for t in tensors):
         return None
@@ -1252,6 +1281,15 @@ class BatchedPPO:
             json.dump(meta, f)
 
     def load_policy(self, path: str) -> None:
+        """Policy weights from safetensors, or from a Stable-Baselines3 checkpoint when the path
+        ends in .zip (ballbot_rl.evaluation.sb3_zip: policy.pth alone, weights only)."""
+        if str(path).lower().endswith(".zip"):
+            from ballbot_rl.evaluation.sb3_zip import policy_state_from_sb3, read_sb3_zip
+
+            state, _ = policy_state_from_sb3(*read_sb3_zip(path), policy=self.policy)
+            self.policy.load_state_dict(state)  # copies in place: FlatAdamW's views stay views
+            self._sync_params()
+            return
         from safetensors.torch import load_file
 
         self.policy.load_state_dict(load_file(path, device=str(self.device)))

@@ -10,7 +10,9 @@ seed, evaluation.*, env.*, problem.terrain/reward).  Differences, by design:
   thousands and lower n_steps (configs in tools/ppo_gpu.yaml);
 * the interactive overwrite/updates-per-rollout confirmations (train.py:194-266)
   become printed warnings -- a batch job cannot answer them;
-* checkpoints are safetensors (no pickled SB3 zip); with a `camera` section the
+* checkpoints are safetensors (no pickled SB3 zip is written; `resume:` also takes an SB3
+  .zip, of which policy.pth alone is read, weights only); `evaluation.fused: true` runs the
+  EvalCallback's evaluations on the device (ballbot_rl.evaluation.DeviceEvaluator); with a `camera` section the
   cameras are on, as in the reference (depth frames, or RGB-D frames and 4-channel
   CNN branches with `camera.disable_rgb: false`); `frozen_cnn` names a depth encoder
   pretrained by ballbot_rl.encoders.pretrain (safetensors) -- the reference's
@@ -174,7 +176,8 @@ def main(config: Dict[str, Any], seed: int, out: Optional[str] = None, total_tim
             else:
                 hooks["callback_after_eval"] = recorder if freq == "every_eval" else EveryNth(recorder, freq)
         on_rollout = EvalCallback(eval_env, n_eval_episodes=n_eval, eval_freq=eval_freq, n_total_envs=n_total,
-                                  log_path=out_path / "results", best_model_save_path=out_path, **hooks)
+                                  log_path=out_path / "results", best_model_save_path=out_path,
+                                  fused=bool(eval_cfg.get("fused", False)), **hooks)
 
     total = int(float(total_timesteps if total_timesteps is not None else config["total_timesteps"]))
     model.learn(total_timesteps=total, rollout_callback=on_rollout)

@@ -52,6 +52,10 @@ __device__ __forceinline__ const float* image_of(const EncArgs& a, long long b) 
   return a.images + (a.index ? a.index[b] : b) * a.image_stride;
 }
 
+// a negative index entry skips its row: nothing is read for it and its out row is left alone (eval
+// mode; the C-ABI refuses it in train mode, and no kernel here forms an address from it)
+__device__ __forceinline__ bool skipped(const EncArgs& a, long long b) { return a.index && a.index[b] < 0; }
+
 __device__ __forceinline__ void stage_image(float (*x)[IW], const float* img) {
   for (int e = threadIdx.x; e < IH * IW / 4; e += 256)
     reinterpret_cast<float4*>(&x[0][0])[e] = reinterpret_cast<const float4*>(img)[e];
@@ -95,6 +99,7 @@ __global__ __launch_bounds__(256) void conv1_moments_kernel(EncArgs a) {
   for (int i = 0; i < MOM_IMGS; i++) {
     const long long b = (long long)blockIdx.x * MOM_IMGS + i;
     if (b >= a.n) break;
+    if (skipped(a, b)) continue;  // workgroup-uniform
     __syncthreads();
     stage_image(x, image_of(a, b));
     __syncthreads();
@@ -239,7 +244,8 @@ __global__ __launch_bounds__(512) void conv2_kernel(EncArgs a) {
     if (producer && st < nitems) {
       const long long b = blockIdx.x + (st >> 2) * (long long)gridDim.x;
       const int quarter = int(st & 3), buf = int(st & 1);
-      if (quarter == 0) {
+      const bool live = !skipped(a, b);  // workgroup-uniform: a skipped image's four items pass empty
+      if (live && quarter == 0) {
         const float* img = image_of(a, b);
 #pragma unroll
         for (int j = 0; j < H1 * H1 / 256; j++) {
@@ -254,7 +260,7 @@ __global__ __launch_bounds__(512) void conv2_kernel(EncArgs a) {
         }
       }
 #pragma unroll
-      for (int j = 0; j < H1 * H1 / 256; j++) {
+      for (int j = 0; live && j < H1 * H1 / 256; j++) {
         const int pos = t8 + 256 * j;
 #pragma unroll
         for (int icl = 0; icl < QCH; icl++) {  // uniform channel: scalar weight loads
@@ -263,7 +269,7 @@ __global__ __launch_bounds__(512) void conv2_kernel(EncArgs a) {
         }
       }
     }
-    if (!producer && st >= 1) {
+    if (!producer && st >= 1 && !skipped(a, blockIdx.x + ((st - 1) >> 2) * (long long)gridDim.x)) {
       const long long it = st - 1;
       const long long b = blockIdx.x + (it >> 2) * (long long)gridDim.x;
       const int quarter = int(it & 3), buf = int(it & 1);
@@ -333,7 +339,7 @@ __global__ __launch_bounds__(256) void linear_kernel(EncArgs a) {
   if (t < 2 * C1) ss2[t] = a.ws.ss2[t];
   __syncthreads();
   const long long img = (long long)blockIdx.x * 32 + r32;
-  const bool ok_img = img < a.n;
+  const bool ok_img = img < a.n && !skipped(a, img);
   const bool ok_j = r32 < NZ;
   const float* arow = a.ws.out2 + (ok_img ? img : 0) * FL + 4 * hh;
   const float* wrow = a.p.wl + (ok_j ? r32 : 0) * FL + 4 * hh;
@@ -418,7 +424,7 @@ __global__ __launch_bounds__(256) void head_kernel(EncArgs a, int nparts) {
   }
   __syncthreads();
   const long long e = (long long)blockIdx.x * 256 + t;
-  if (e < a.n * NZ) {
+  if (e < a.n * NZ && !skipped(a, e / NZ)) {
     const int j = int(e % NZ);
     a.out[(e / NZ) * a.out_stride + j] = tanhf(fmaf(a.ws.z[e], sc[j], sh[j]));
   }

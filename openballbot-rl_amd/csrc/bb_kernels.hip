@@ -45,6 +45,7 @@
 #include "bb_ppo.h"
 #include "bb_mlp.h"
 #include "bb_encoder.h"
+#include "bb_eval.h"
 #include "bb_pairmap.h"
 
 using namespace bb;
@@ -3034,6 +3035,22 @@ int bb_depth_encoder(const bb_encoder_params* p, const float* images, int64_t im
   if (out_stride < 20) return fail("bb_depth_encoder: out_stride must be >= 20");
   if (ws_bytes < encoder_workspace_bytes(n))
     return fail("bb_depth_encoder: workspace of %lld bytes < %lld", (long long)ws_bytes, encoder_workspace_bytes(n));
+  if (train && index && n > 0) {
+    // a negative entry skips its row (eval mode only): batch statistics need every row.  The index is
+    // device memory, so this check reads it back -- outside a stream capture only (a captured
+    // train-mode call cannot be checked: non-negative entries are then the caller's contract)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
+      std::vector<long long> host(static_cast<size_t>(n));
+      HIPCHK(hipMemcpyAsync(host.data(), index, sizeof(long long) * size_t(n), hipMemcpyDeviceToHost,
+                            (hipStream_t)stream));
+      HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+      for (int64_t i = 0; i < n; i++)
+        if (host[size_t(i)] < 0)
+          return fail("bb_depth_encoder: index[%lld] = %lld is negative in train mode (a skipped row: eval mode only)",
+                      (long long)i, host[size_t(i)]);
+    }
+  }
   EncArgs a{};
   a.p = EncParams{p->conv1_w, p->conv1_b, p->bn1_w, p->bn1_b, p->bn1_mean, p->bn1_var,
                   reinterpret_cast<long long*>(p->bn1_count), p->conv2_w, p->conv2_b, p->bn2_w, p->bn2_b,
@@ -3044,6 +3061,25 @@ int bb_depth_encoder(const bb_encoder_params* p, const float* images, int64_t im
   a.momentum = momentum; a.eps = eps; a.out = out; a.out_stride = out_stride;
   if (launch_encoder(a, ws, (hipStream_t)stream))
     return fail("bb_depth_encoder: launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
+int bb_eval_track(const bb_eval_args* a, void* stream) {
+  // argument checks first (none of them touches HIP)
+  if (!a) return fail("bb_eval_track: NULL args");
+  if (a->n < 1) return fail("bb_eval_track: n must be >= 1 (got %d)", a->n);
+  if (!a->obs && (a->feats || a->fresh)) return fail("bb_eval_track: feats / fresh need obs");
+  if (a->flags) {
+    if (a->cap < 0) return fail("bb_eval_track: cap must be >= 0 (got %d)", a->cap);
+    if (!a->reward || !a->targets || !a->ep_ret || !a->ep_len || !a->counts || !a->book)
+      return fail("bb_eval_track: reward, targets, ep_ret, ep_len, counts and book must be non-NULL with flags");
+    if (a->cap > 0 && (!a->tab_ret || !a->tab_len || !a->tab_env || !a->tab_step))
+      return fail("bb_eval_track: the episode table (tab_ret, tab_len, tab_env, tab_step) must be non-NULL");
+  }
+  const EvalArgs e{a->n, a->cap, a->reward, a->flags, a->obs, a->rel_ts, a->targets, a->ep_ret, a->ep_len,
+                   a->counts, a->tab_ret, a->tab_len, a->tab_env, a->tab_step, a->book, a->feats, a->fresh};
+  if (launch_eval_track(e, (hipStream_t)stream))
+    return fail("bb_eval_track: launch failed: %s", hipGetErrorString(hipGetLastError()));
   return 0;
 }
 
