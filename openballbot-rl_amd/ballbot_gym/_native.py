@@ -11,11 +11,12 @@ from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "_lib" / "libbb_mi355x.so"
-# bb_kernels.hip with the forward's twin forms and once-per-launch model terms compiled out (the serial
-# pre-phase, csrc/bb_physics.h), linked with the product's other objects: the reference build that
-# tests/test_gpu_prephase.py holds the product to, bit for bit
+# bb_kernels.hip with the forward's twin forms, once-per-launch model terms and batched LDS reads compiled
+# out (the serial pre-phase, csrc/bb_physics.h), linked with the product's other objects: the reference
+# build that tests/test_gpu_prephase.py and tests/test_gpu_pre_batch.py hold the product to, bit for bit
 SERIAL_LIB_PATH = PKG / "_lib" / "libbb_mi355x_serial.so"
-SERIAL_FLAGS = ["-DBB_NO_TWIN_KIN", "-DBB_NO_TWIN_POS", "-DBB_NO_TWIN_BIAS", "-DBB_NO_MODEL_ONCE"]
+SERIAL_FLAGS = ["-DBB_NO_TWIN_KIN", "-DBB_NO_TWIN_POS", "-DBB_NO_TWIN_BIAS", "-DBB_NO_MODEL_ONCE",
+                "-DBB_NO_PRE_BATCH"]
 CSRC = PKG.parent / "csrc"
 INCLUDE = PKG.parent.parent / "include"
 

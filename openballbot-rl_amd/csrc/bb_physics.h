@@ -119,6 +119,38 @@ struct ModelT {
 #endif
 constexpr int TWIN_L = 16;  // the team size the twin forms are written for
 
+// Device code: nothing is scheduled across this point.  One wave per SIMD hides no latency, and
+// with the register file full the compiler sinks each LDS read to its use, so a chain of
+// products waits out one read's latency per pair of operands; the fence keeps a batch of reads
+// issued together above the arithmetic that consumes them.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define BB_ISSUE_FENCE() __builtin_amdgcn_sched_barrier(0)
+#else
+#define BB_ISSUE_FENCE() ((void)0)
+#endif
+
+// Forward outside the Newton loop, LDS reads issued ahead of use (the FUSE kernels only; DESIGN 6,
+// round 12): a section's workspace operands are loaded into locals in one batch, BB_ISSUE_FENCE,
+// then the parent's arithmetic on the parent's operands in the parent's order: the same bits.
+//   kPreBatchRk     rk4_step's sums after a stage's solve: W.vi, vs and as read in one batch and
+//                   qacc taken from the registers it is in (the serial form stores it to the
+//                   workspace, reads it back and waits on every read-modify-write pair)
+//   kPreBatchDense  mass_dense_team: the eight entries a lane copies are addressed by
+//                   mass_entry_off and read back to back (the serial form walks mass_entry's
+//                   branch tree under exec masks, one exposed read per leaf and entry)
+// -DBB_NO_PRE_BATCH_RK / _DENSE turn the items off one by one, -DBB_NO_PRE_BATCH both (A/B
+// builds, and the serial reference library of the tests).
+#if defined(BB_NO_PRE_BATCH) || defined(BB_NO_PRE_BATCH_RK)
+constexpr bool kPreBatchRk = false;
+#else
+constexpr bool kPreBatchRk = true;
+#endif
+#if defined(BB_NO_PRE_BATCH) || defined(BB_NO_PRE_BATCH_DENSE)
+constexpr bool kPreBatchDense = false;
+#else
+constexpr bool kPreBatchDense = true;
+#endif
+
 // Terms of the forward that depend on the model alone (model_once fills them with the forward's
 // own expressions).  [0] / [1] of bc, bI, bm: the base composite / the ball, the two operand sets
 // of bias_finish's body_force.

@@ -3,6 +3,11 @@
 // product's flags, so that the kernels of bb_kernels.hip's own unit are compiled exactly as they
 // were before this kernel existed (see bb_pid_rollout_launch_tu in bb_kernels.hip).
 #define BB_PID_TU
+// no batched pre-phase reads in this unit (bb_physics.h; the same bits either way): its fp64 fast
+// kernel is at the 512-register limit with scratch, so its forward keeps the serial text
+#ifndef BB_NO_PRE_BATCH
+#define BB_NO_PRE_BATCH
+#endif
 #ifdef BB_PHASE_CLOCKS  // diagnostic builds: this unit's counters under their own name
 #define bb_phase_cycles bb_phase_cycles_pid
 #endif

@@ -116,6 +116,20 @@ BB_HD void tri_unpack(int e, int& i, int& j) {
   j = e - r * (r + 1) / 2;
 }
 
+// tri_unpack for 0 <= e < NH without the square root and the loops: i is the number of row starts
+// k (k + 1) / 2, k = 1 .. NV - 1, at or below e, and the last of them is where row i starts.
+BB_HD void tri_unpack_count(int e, int& i, int& j) {
+  int r = 0, s = 0;
+#pragma unroll
+  for (int k = 1; k < NV; k++) {
+    const bool in = e >= k * (k + 1) / 2;
+    r += in ? 1 : 0;
+    s = in ? k * (k + 1) / 2 : s;
+  }
+  i = r;
+  j = e - s;
+}
+
 // What mjData holds after the last forward of mj_step (RK stage 4).
 template <typename T>
 struct StageOut {
@@ -197,6 +211,35 @@ BB_HD T mass_entry(const Mass<T>& M, int i, int j) {
   return i == j ? M.MBrr[i - 12] : T(0);
 }
 
+// mass_entry as an address: the offset of entry (i >= j) in Mass<T> taken as an array of T, or
+// -1 where the entry is zero.  Integer work only, so that a lane can address several entries and
+// read them back to back (mass_dense_team) instead of walking mass_entry's branches per entry.
+template <typename T>
+BB_HD int mass_entry_off(int i, int j) {
+  static_assert(sizeof(Mass<T>) == 53 * sizeof(T), "Mass<T> is 53 values of T, nothing else");
+  constexpr int MT = offsetof(Mass<T>, mt) / sizeof(T), MTR = offsetof(Mass<T>, Mtr) / sizeof(T),
+                MRR = offsetof(Mass<T>, Mrr) / sizeof(T), MTH = offsetof(Mass<T>, Mth) / sizeof(T),
+                MRH = offsetof(Mass<T>, Mrh) / sizeof(T), MHH = offsetof(Mass<T>, Mhh) / sizeof(T),
+                MB = offsetof(Mass<T>, mB) / sizeof(T), MBTR = offsetof(Mass<T>, MBtr) / sizeof(T),
+                MBRR = offsetof(Mass<T>, MBrr) / sizeof(T);
+  if (i < 3) return i == j ? MT : -1;
+  if (i < 6) {
+    if (j < 3) return MTR + 3 * j + (i - 3);
+    const int a = i - 3, b = j - 3;
+    return MRR + (a == b ? a : a + b + 2);
+  }
+  if (i < 9) {
+    const int w = i - 6;
+    if (j < 3) return MTH + 3 * w + j;
+    if (j < 6) return MRH + 3 * w + (j - 3);
+    return j == i ? MHH + w : -1;
+  }
+  if (j < 9) return -1;
+  if (i < 12) return i == j ? MB : -1;
+  if (j < 12) return MBTR + 3 * (j - 9) + (i - 12);
+  return i == j ? MBRR + (i - 12) : -1;
+}
+
 // position of dof i among wheel w's 13 contact columns, or -1
 BB_HD int wheel_pos(int i, int w) { return i < 6 ? i : (i == 6 + w ? 6 : (i >= 9 ? i - 2 : -1)); }
 
@@ -211,16 +254,6 @@ BB_HD T wheel_dot(const WheelCon<T>& C, int w, int r, const T* x) {
   for (int i = 7; i < 13; i++) acc += C.J[r][i] * x[i + 2];
   return acc;
 }
-
-// Device code: nothing is scheduled across this point.  One wave per SIMD hides no latency, and
-// with the register file full the compiler sinks each LDS read to its use, so a chain of
-// products waits out one read's latency per pair of operands; the fence keeps a batch of reads
-// issued together above the arithmetic that consumes them.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define BB_ISSUE_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define BB_ISSUE_FENCE() ((void)0)
-#endif
 
 // J x for the three rows of wheel contact w at once: each row is wheel_dot's chain (J[r][6]
 // x_hinge, then columns 0..5, then 7..12: the same bits), the 39 entries of J and the three of

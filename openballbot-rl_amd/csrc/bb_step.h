@@ -13,10 +13,15 @@ namespace bb {
 //   1 stage state   2 kinematics   3 wheel lanes   4 mass_finish   5 bias_finish   6 collision
 //   7 stage out, dense mass, ground setup   8 solve   9 after the solve, RK sums
 //   10 mj_advance   11 obs, reward, termination (to the kernel's end)
+// BB_PRE_ARM(k, arm): inside section k, the start of the twin arm (16-lane teams of the FUSE
+// kernels), of the serial arm (other team sizes) and of the code after the two (join), so that
+// the table can be read for the arm that runs.
 #if defined(BB_ISA_MARKS) && defined(__HIP_DEVICE_COMPILE__)
 #define BB_PRE(k) asm volatile("; PRE_MARK " #k);
+#define BB_PRE_ARM(k, arm) asm volatile("; PRE_MARK " #k " " #arm);
 #else
 #define BB_PRE(k)
+#define BB_PRE_ARM(k, arm)
 #endif
 
 // Env configuration (BBotSimulation.__init__, ballbot_env.py:221-231).
@@ -67,13 +72,18 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
   // base/ball frames on every lane (twin: one per half), wheel w's frame on lane w
 #if BB_TWIN_KIN
   if (twin) {
+    BB_PRE_ARM(2, twin)
     T qn[4];
     kinematics_half(m, q, hi, k, qn);
     // the stage out's quat_b is the base half's normalised quaternion (same expression, same input)
     if (so && !hi) { so->quat_b[0] = qn[0]; so->quat_b[1] = qn[1]; so->quat_b[2] = qn[2]; so->quat_b[3] = qn[3]; }
   } else
 #endif
+  {
+    BB_PRE_ARM(2, serial)
     kinematics_base(m, q, k);
+  }
+  BB_PRE_ARM(2, join)
   if (tm.tl < 3) kinematics_wheel(m, q, tm.tl, k, mo);
   team_sync();
 #else
@@ -108,6 +118,7 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
 #if BB_TWIN_BIAS
     if (twin) {
       // each half its own body's six entries; W.vi holds v (copied above if it came from elsewhere)
+      BB_PRE_ARM(5, twin)
       T b6[6];
       bias_finish_half(m, k, W.vi, fw, hi, b6, mo);
       T* qo = W.qfs + half_vlin(hi);
@@ -116,12 +127,14 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
     } else
 #endif
     {
+      BB_PRE_ARM(5, serial)
       T qfs[NV];
       bias_finish(m, k, v, fw, qfs, mo);
 #pragma unroll
       for (int i = 0; i < NV; i++)
         if (i < 6 || i > 8) W.qfs[i] = -qfs[i];
     }
+    BB_PRE_ARM(5, join)
     team_sync();  // W.H free again (candidate list of the body collision)
   }
 #else
@@ -224,7 +237,7 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
   }
 #ifdef __HIP_DEVICE_COMPILE__
   // 16-lane DPP-row solve: smooth force and dense M staged in the team's LDS
-  t16::mass_dense_team(W, tm.tl);
+  t16::mass_dense_team<FUSE && kPreBatchDense>(W, tm.tl);
   team_sync();
   if constexpr (!BODY) t16::ground_setup(m, W, ng, tm.tl);  // into the mass blocks: after mass_dense_team
 
@@ -269,6 +282,30 @@ BB_HD bool vec_bad(const T* x, int n) {  // MuJoCo's mju_isBad over x[0..n): NaN
   return bad;
 }
 
+// One stage's share of the RK4 sums, vs (+)= b vi and as (+)= b a (the first stage starts them and
+// keeps a in k1), with the workspace operands vi, vs and as read in one batch ahead of the
+// arithmetic and the results stored after it (kPreBatchRk, bb_physics.h).  rk4_step's serial text
+// reads, adds and stores entry by entry; the products, their operands and the sums are the same.
+template <typename T>
+BB_HD void rk_sums_batch(bool first, T b, const T* vi, const T* a, T* vs, T* as, T* k1) {
+  T vl[NV], sv[NV], sa[NV];
+#pragma unroll
+  for (int i = 0; i < NV; i++) vl[i] = vi[i];
+  if (first) {
+    BB_ISSUE_FENCE();
+#pragma unroll
+    for (int i = 0; i < NV; i++) { sv[i] = b * vl[i]; sa[i] = b * a[i]; k1[i] = a[i]; }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NV; i++) { sv[i] = vs[i]; sa[i] = as[i]; }
+    BB_ISSUE_FENCE();
+#pragma unroll
+    for (int i = 0; i < NV; i++) { sv[i] += b * vl[i]; sa[i] += b * a[i]; }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; i++) { vs[i] = sv[i]; as[i] = sa[i]; }
+}
+
 // mj_step with integrator RK4 = mj_forward + mj_checkAcc + mj_RungeKutta(N=4) + mj_advance.
 // warm: qacc_warmstart (each stage's constraint solve saves its qacc).
 // mj_checkAcc: a bad qacc after the first forward resets the data (qpos0, zero
@@ -304,6 +341,7 @@ BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const Terra
       if (FUSE && tm.L == TWIN_L) {
         // twin form: the positions and hinge angles on every lane, each half its own quaternion
         const bool hi = (tm.tl & 8) != 0;
+        BB_PRE_ARM(1, twin)
         T qh[4];
         if (stage == 0) {
 #pragma unroll
@@ -331,6 +369,7 @@ BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const Terra
       } else
 #endif
       {
+      BB_PRE_ARM(1, serial)
       if (stage == 0) {
 #pragma unroll
         for (int i = 0; i < NV; i++) vi[i] = v0[i];
@@ -346,6 +385,7 @@ BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const Terra
 #pragma unroll
       for (int i = 0; i < NV; i++) W.vi[i] = vi[i];
       }
+      BB_PRE_ARM(1, join)
     }
     // the solve's warm start / result in registers for this forward only
     // (warm may live in the workspace, see step_kernel)
@@ -384,7 +424,9 @@ BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const Terra
 #endif
     const T b = (stage == 0 || stage == 3) ? T(1.0 / 6) : T(1.0 / 3);  // RK4 weights B
     team_sync();
-    if (stage == 0) {
+    if constexpr (FUSE && kPreBatchRk) {
+      rk_sums_batch(stage == 0, b, W.vi, acc, vs, as, W.k1);  // acc: what warm was just set to
+    } else if (stage == 0) {
 #pragma unroll
       for (int i = 0; i < NV; i++) { vs[i] = b * W.vi[i]; as[i] = b * warm[i]; W.k1[i] = warm[i]; }
     } else {
@@ -401,6 +443,7 @@ BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const Terra
   if (FUSE && tm.L == TWIN_L) {
     // twin form; q is the team's shared state (every device caller keeps it in the workspace),
     // so each half stores its own quaternion and a team_sync shows it to the other half
+    BB_PRE_ARM(10, twin)
     const bool hi = (tm.tl & 8) != 0;
 #pragma unroll
     for (int i = 0; i < NQ; i++)
@@ -418,6 +461,7 @@ BB_HD int rk4_step(const ModelT<T>& m, T* q, T* v, T* warm, T* ctrl, const Terra
     return iters;
   }
 #endif
+  BB_PRE_ARM(10, serial)
 #pragma unroll
   for (int i = 0; i < NQ; i++) q[i] = q0[i];
   T vv[NV];

@@ -1747,13 +1747,41 @@ __device__ int collide_body_team(const ModelT<T>& m, const Kin<T>& k, const floa
   return nb;
 }
 
-// dense mass matrix (packed lower) into W.H, entry-parallel; once per forward
-template <typename T>
+// dense mass matrix (packed lower) into W.H, entry-parallel; once per forward.  BATCH (the FUSE
+// kernels with kPreBatchDense, bb_physics.h): a lane's entries e = tl, tl + L, ... are addressed
+// first (mass_entry_off), read back to back and stored after one wait; the same copies.
+template <bool BATCH = false, typename T>
 __device__ __forceinline__ void mass_dense_team(EnvWork<T>& W, int tl) {
-  for (int e = tl; e < NH; e += L) {
-    int i, j;
-    tri_unpack(e, i, j);
-    W.H[e] = mass_entry(W.M, i, j);
+  if constexpr (BATCH) {
+    constexpr int R = (NH + L - 1) / L;
+    const T* Mp = reinterpret_cast<const T*>(&W.M);
+    // The offsets depend on the lane alone.  Hoisted out of the step loop they would occupy 22
+    // registers across the solve (the fp64 multi-step kernel then spills); the empty asm makes the
+    // lane index opaque here, so they are formed again in every forward, as the serial form's are.
+    asm volatile("" : "+v"(tl));
+    tl &= L - 1;
+    int o[R];
+    T x[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const int e = tl + r * L;
+      int i, j;
+      tri_unpack_count(e < NH ? e : NH - 1, i, j);
+      o[r] = mass_entry_off<T>(i, j);
+      x[r] = Mp[o[r] < 0 ? 0 : o[r]];
+    }
+    BB_ISSUE_FENCE();
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const int e = tl + r * L;
+      if (e < NH) W.H[e] = o[r] < 0 ? T(0) : x[r];
+    }
+  } else {
+    for (int e = tl; e < NH; e += L) {
+      int i, j;
+      tri_unpack(e, i, j);
+      W.H[e] = mass_entry(W.M, i, j);
+    }
   }
 }
 

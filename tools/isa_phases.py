@@ -22,6 +22,11 @@ moves (v_accvgpr_*).  A section is the text from its mark to the next mark of ei
 code before the first mark is the kernel prologue, the solve's PHASE_MARK sections are summed
 into "solve".  Where the compiler duplicated a section (both arms of the team-size test, a peeled
 loop) the copies add up, so the serial fall-back of the twin forms is listed with them.
+Five more columns count the LDS traffic and its waits: ds_read*, ds_write*, s_waitcnt, those of
+them that wait for lgkmcnt(0), and read-wait as defined above.  The sections that hold a twin
+arm and a serial arm carry sub-marks (`; PRE_MARK k twin|serial|join`, BB_PRE_ARM): under such a
+section's row its parts are listed, "head" being the code before the first arm; the twin rows
+are what a 16-lane team of the FUSE kernels runs.
 
   python tools/isa_phases.py --pre /tmp/bbk.s
 """
@@ -123,22 +128,27 @@ PRE_NAMES = {0: "kernel prologue", 1: "stage state", 2: "kinematics", 3: "wheel 
              9: "after the solve, RK sums", 10: "mj_advance", 11: "obs, reward, termination, stores"}
 
 
+PRE_COLS = (("all", "all"), ("VALU", "valu"), ("FP64", "fp64"), ("rcp+rsq", "rcp"), ("lane", "lane"), ("AGPR", "agpr"),
+            ("ds_read", "dsr"), ("ds_write", "dsw"), ("waitcnt", "wait"), ("lgkm(0)", "lgkm0"), ("read-wait", "rwait"))
+
+
 def pre_main(path, want):
     func, cur, counts = None, None, {}
+    since_read = None  # instructions since the last ds_read*, None when there was none in this part
     for line in open(path):
         m = re.match(r"^(_Z[^:\s]+):", line)
         if m:
-            func, cur = m.group(1), 0
+            func, cur, since_read = m.group(1), (0, ""), None
             continue
         if func is None or want not in func:
             continue
-        m = re.search(r"; PRE_MARK (\d+)", line)
+        m = re.search(r"; PRE_MARK (\d+)(?: (\w+))?", line)
         if m:
-            cur = int(m.group(1))
+            cur, since_read = (int(m.group(1)), m.group(2) or "head"), None
             continue
         m = re.search(r"; PHASE_MARK (\d+)", line)
         if m:
-            cur = 9 if int(m.group(1)) == 7 else 8  # PH(7): the solver's exit
+            cur, since_read = ((9 if int(m.group(1)) == 7 else 8), "head"), None  # PH(7): the solver's exit
             continue
         s = line.strip()
         if not s or s.startswith((";", ".")) or s.endswith(":"):
@@ -147,7 +157,7 @@ def pre_main(path, want):
             func = None
             continue
         op = s.split()[0]
-        c = counts.setdefault(func, {}).setdefault(cur, Counter())
+        c = counts.setdefault(func, {}).setdefault(cur[0], {}).setdefault(cur[1], Counter())
         c["all"] += 1
         if op.startswith("v_"):
             c["valu"] += 1
@@ -159,17 +169,37 @@ def pre_main(path, want):
             c["lane"] += 1
         if op.startswith("v_accvgpr"):
             c["agpr"] += 1
+        if op.startswith("ds_write"):
+            c["dsw"] += 1
+        if op == "s_waitcnt":
+            c["wait"] += 1
+            if "lgkmcnt(0)" in s:
+                c["lgkm0"] += 1
+        # read-wait, as in the solver mode: everything outstanding is waited for within three
+        # instructions of an LDS read's issue
+        if op.startswith("ds_read"):
+            c["dsr"] += 1
+            since_read = 0
+        elif since_read is not None:
+            since_read += 1
+            if op == "s_waitcnt" and "lgkmcnt(0)" in s and since_read <= 3:
+                c["rwait"] += 1
+    fmt = "  %-38s" + " %9s" * len(PRE_COLS)
     for func, secs in counts.items():
         print(func[:100])
-        print("  %-38s %6s %6s %6s %8s %6s %6s" % ("section", "all", "VALU", "FP64", "rcp+rsq", "lane", "AGPR"))
+        print(fmt % (("section",) + tuple(h for h, _ in PRE_COLS)))
         tot = Counter()
         for k in sorted(secs):
-            c = secs[k]
+            c = Counter()
+            for part in secs[k].values():
+                c.update(part)
             tot.update(c)
-            print("  %-38s %6d %6d %6d %8d %6d %6d" % (PRE_NAMES.get(k, str(k)), c["all"], c["valu"], c["fp64"], c["rcp"],
-                                                       c["lane"], c["agpr"]))
-        print("  %-38s %6d %6d %6d %8d %6d %6d" % ("total", tot["all"], tot["valu"], tot["fp64"], tot["rcp"], tot["lane"],
-                                                   tot["agpr"]))
+            print(fmt % ((PRE_NAMES.get(k, str(k)),) + tuple(c[f] for _, f in PRE_COLS)))
+            if len(secs[k]) > 1:
+                for arm in ("head", "twin", "serial", "join"):
+                    if arm in secs[k]:
+                        print(fmt % (("    " + arm,) + tuple(secs[k][arm][f] for _, f in PRE_COLS)))
+        print(fmt % (("total",) + tuple(tot[f] for _, f in PRE_COLS)))
 
 
 if __name__ == "__main__":
