@@ -1167,6 +1167,69 @@ BB_HD void body_ls_terms(const ModelT<T>& m, const T* bc, const Poses<T>& P, con
   D = b.D;
 }
 
+// The ball-terrain pass of the step kernels (t16::collide_team) walks only the prisms the ball can
+// reach.  -DBB_NO_PRISM_WINDOW: the whole sub-grid under the ball's AABB, as
+// collide_ground below walks it (A/B builds, and the serial reference library of the tests).
+#ifndef BB_NO_PRISM_WINDOW
+constexpr bool kPrismWindow = true;
+#else
+constexpr bool kPrismWindow = false;
+#endif
+
+// "no bound" for prism_window's Z: above any centre that passes its AABB test
+template <typename T> BB_HD constexpr T prism_no_bound() { return T(3.0e38); }
+
+// The cell window [cmin, cmax] x [rmin, rmax] of the prisms a ball at c has to test: false when
+// collide_ground's AABB test rejects the ball (no prism; a NaN centre too).  First the sub-grid
+// under the ball's AABB, c +- r, in collide_ground's text.  Z bounds the window's vertices from
+// above: T(h) * size_z <= Z for every vertex h of that sub-grid.  Below the centre, every prism
+// there has ez >= c[2] - Z in collide_ground's coarse test ex^2 + ey^2 + ez^2 <= r^2, which can
+// then only pass with ex, ey <= rho = sqrt(r^2 - (c[2] - Z)^2): the prism's xy box meets
+// c +- rho.  The window is cut to the sub-grid under c +- rho', same floor / ceil / clamp, with
+// rho' = rho widened by mrg = r 2^-10 on both sides of the square root (88 um; a float ulp at
+// 5 m is 0.5 um).  The margin also makes the inequality strict, so a prism whose box only
+// touches c +- rho stays inside.  Rows and columns are cut from both ends, which keeps the
+// row-major sliding-window order of what is left, and a prism's parity (which triangle of its
+// cell it is) does not depend on cmin.  With Z at or above c[2] - mrg, or NaN, the window is the
+// AABB's, bit for bit.
+template <typename T>
+BB_HD bool prism_window(const ModelT<T>& m, const T* c, T size_z, T Z, int& cmin, int& cmax, int& rmin, int& rmax) {
+  const T r = m.ball_r;
+  const T sx = m.hf_sx, sy = m.hf_sy, zb = m.hf_bottom;
+  const T xmin = c[0] - r, xmax = c[0] + r, ymin = c[1] - r, ymax = c[1] + r, zmin = c[2] - r, zmax = c[2] + r;
+  // negated form: a NaN ball position (diverged stage state) forms no cell index
+  if (!(xmin <= sx && xmax >= -sx && ymin <= sy && ymax >= -sy && zmin <= size_z && zmax >= -zb)) return false;
+  const int N1 = HF_N - 1;
+  cmin = (int)floor((xmin + sx) / (2 * sx) * N1);
+  cmax = (int)ceil((xmax + sx) / (2 * sx) * N1);
+  rmin = (int)floor((ymin + sy) / (2 * sy) * N1);
+  rmax = (int)ceil((ymax + sy) / (2 * sy) * N1);
+  cmin = cmin < 0 ? 0 : cmin;
+  cmax = cmax > N1 ? N1 : cmax;
+  rmin = rmin < 0 ? 0 : rmin;
+  rmax = rmax > N1 ? N1 : rmax;
+  if constexpr (kPrismWindow) {
+    const T mrg = r * T(1.0 / 1024);
+    const T e0 = (c[2] - Z) - mrg;
+    if (e0 > 0) {
+      const T rho = minT(r, sqrt(maxT(T(0), r * r - e0 * e0)) + mrg);
+      int c0 = (int)floor((c[0] - rho + sx) / (2 * sx) * N1);
+      int c1 = (int)ceil((c[0] + rho + sx) / (2 * sx) * N1);
+      int r0 = (int)floor((c[1] - rho + sy) / (2 * sy) * N1);
+      int r1 = (int)ceil((c[1] + rho + sy) / (2 * sy) * N1);
+      c0 = c0 < 0 ? 0 : c0;
+      c1 = c1 > N1 ? N1 : c1;
+      r0 = r0 < 0 ? 0 : r0;
+      r1 = r1 > N1 ? N1 : r1;
+      cmin = c0 > cmin ? c0 : cmin;
+      cmax = c1 < cmax ? c1 : cmax;
+      rmin = r0 > rmin ? r0 : rmin;
+      rmax = r1 < rmax ? r1 : rmax;
+    }
+  }
+  return true;
+}
+
 // mjc_ConvexHField for the ball: sub-grid from the ball AABB, triangular
 // prisms in MuJoCo's sliding-window order, one contact per penetrated prism.
 // Writes normal/lever/aref/D into the store; returns the contact count.

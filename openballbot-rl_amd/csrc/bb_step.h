@@ -160,7 +160,8 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
 #endif
 #ifdef __HIP_DEVICE_COMPILE__
   BB_PRE(6)
-  const int ng = tr.hf ? t16::collide_team(m, k, v, tr.hf, tr.size_z, W.g, &overflow, tm.tl, mo) : 0;
+  // tr.hz = T(max h) * size_z bounds every vertex T(h) * size_z (the rounding is monotone): 0 on flat ground
+  const int ng = tr.hf ? t16::collide_team(m, k, v, tr.hf, tr.size_z, W.g, &overflow, tm.tl, mo, tr.hz) : 0;
   int nb = 0;
   if constexpr (BODY) {
 #if defined(BB_PHASE_CLOCKS)

@@ -1291,26 +1291,20 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
 // ball's AABB are enumerated in MuJoCo's order (row-major over the sub-grid,
 // two triangles per cell in sliding-window order), 16 per round, one per
 // lane; hits are compacted in that order with a ballot, so the contact list
-// (and the MAXG cap) is exactly the serial one.
+// (and the MAXG cap) is exactly the serial one.  zbound: an upper bound of the
+// sub-grid's vertex heights (T(h) * size_z), by which prism_window leaves out
+// rows and columns whose prisms cannot pass the coarse test; the default is
+// no bound, the whole sub-grid.
 template <typename T>
 __device__ __forceinline__ int collide_team(const ModelT<T>& m, const Kin<T>& k, const T* v, const float* hf,
                                             T size_z, T* g, int* overflow, int tl,
-                                            const ModelOnce<T>* mo = nullptr) {
+                                            const ModelOnce<T>* mo = nullptr, T zbound = prism_no_bound<T>()) {
   const T r = m.ball_r;
   const T* c = k.c;
   const T sx = m.hf_sx, sy = m.hf_sy, zb = m.hf_bottom;
-  const T xmin = c[0] - r, xmax = c[0] + r, ymin = c[1] - r, ymax = c[1] + r, zmin = c[2] - r, zmax = c[2] + r;
-  // negated form: a NaN ball position (diverged stage state) forms no cell index
-  if (!(xmin <= sx && xmax >= -sx && ymin <= sy && ymax >= -sy && zmin <= size_z && zmax >= -zb)) return 0;
-  const int N1 = HF_N - 1;
-  int cmin = (int)floor((xmin + sx) / (2 * sx) * N1);
-  int cmax = (int)ceil((xmax + sx) / (2 * sx) * N1);
-  int rmin = (int)floor((ymin + sy) / (2 * sy) * N1);
-  int rmax = (int)ceil((ymax + sy) / (2 * sy) * N1);
-  cmin = cmin < 0 ? 0 : cmin;
-  cmax = cmax > N1 ? N1 : cmax;
-  rmin = rmin < 0 ? 0 : rmin;
-  rmax = rmax > N1 ? N1 : rmax;
+  const T zmin = c[2] - r;
+  int cmin, cmax, rmin, rmax;
+  if (!prism_window(m, c, size_z, zbound, cmin, cmax, rmin, rmax)) return 0;
   const int ncol = cmax - cmin + 1;
   const int np = 2 * ncol - 2;            // prisms per grid row
   const int total = (rmax - rmin) * (np > 0 ? np : 0);
