@@ -4,10 +4,24 @@
 //   ball   x {tower cylinder, cam sticks}                   (sphere-cylinder / sphere-capsule)
 // (ballast: contype 0; cam cone meshes: asset absent from the reference).
 // Per prism the minimum-translation penetration by the separating-axis
-// theorem: exact for capsule-prism (prism face normals + segment x edges),
-// cylinder-prism adds the cylinder axis, axis x edges and vertex radials
-// (exact except rim-edge contacts).  Same algorithm as the oracle
-// (oracle/bb_oracle.c: capsule_prism, cylinder_prism, sphere_cylinder).
+// theorem over a subset of the axes, so a depth is never too small and can be
+// too large.  Same algorithm as the oracle (oracle/bb_oracle.c: capsule_prism,
+// cylinder_prism, sphere_cylinder); measured against a Minkowski-hull
+// reference (tests/bodycon_ref.py, tests/test_host_bodycon.py) on its case set:
+//   capsule-prism   prism face normals + segment x {z, three top edges}, no
+//     segment x bottom edge.  Exact (16 eps L) while the segment's lower end is
+//     more than 3 cm above the prism's bottom plane (1298 cases, separated and
+//     intersecting).  With that end within 2 cm of the bottom plane and the
+//     segment inside the prism, 30 of 160 depths are too large, by up to 11.3 mm.
+//   cylinder-prism  adds the cylinder axis, axis x {z, top edges} and the vertex
+//     radials; no rim x edge axis.  Exact (within the reference's 8.3e-6 m
+//     bracket) on cap, wall and face contacts.  Where the true contact is the
+//     rim against a prism edge (the hull's normal neither along nor across the
+//     axis), 5 of 5 such contacts among 49 are too deep, by 1.2 to 11.6 mm.
+//     Nothing in the axis set separates a rim from an edge, so this class
+//     includes contacts reported between shapes that are apart (none of the 6
+//     separated rim x edge poses of the set; other poses gave up to 19 mm).
+// Neither reaches an upright robot; both act on toppled ones.
 #pragma once
 
 #include "bb_physics.h"
@@ -449,9 +463,13 @@ BB_HD bool cylinder_prism(const Seg<T>& g, const PrismG<T>& P, T& dist, T* n, T*
   const T na2 = dot3(n, g.a);
   T rad[3] = {n[0] - na2 * g.a[0], n[1] - na2 * g.a[1], n[2] - na2 * g.a[2]};
   const T rl = sqrt(dot3(rad, rad));
-  const T along = fabs(na2) > T(1e-9) ? (na2 > 0 ? -g.hh : g.hh) : clampT(dot3(dc, g.a), -g.hh, g.hh);
+  // n along the axis (a cap) or across it (the wall) leaves n.a or the radial part a rounding residue:
+  // below 1e-9 at fp64, but a few 1e-8 at fp32, where the old 1e-9 took the residue for a direction --
+  // a cap contact's pos went r along the axis, a wall contact's to the cylinder's end
+  const T tiny = sizeof(T) == 8 ? T(1e-9) : T(1e-4);
+  const T along = fabs(na2) > tiny ? (na2 > 0 ? -g.hh : g.hh) : clampT(dot3(dc, g.a), -g.hh, g.hh);
   T sp[3] = {g.c[0] + along * g.a[0], g.c[1] + along * g.a[1], g.c[2] + along * g.a[2]};
-  if (rl > T(1e-9)) {
+  if (rl > tiny) {
 #pragma unroll
     for (int k = 0; k < 3; k++) sp[k] -= g.r * rad[k] / rl;
   } else {
@@ -505,6 +523,15 @@ BB_HD bool sphere_cylinder(const T* c, T r, const Seg<T>& g, T& dist, T* n, T* p
   } else {
     const T ds = g.r - rho, dcap = g.hh - fabs(z);
     if (ds < dcap) {
+      if (!(rho > T(1e-12))) {
+        // the centre on the axis: every direction across it is as deep; take one (u = 0 made n = 0)
+        const T ax = fabs(g.a[0]), ay = fabs(g.a[1]), az = fabs(g.a[2]);
+        const T e[3] = {ax <= ay && ax <= az ? T(1) : T(0), ax <= ay && ax <= az ? T(0) : (ay <= az ? T(1) : T(0)),
+                        ax <= ay && ax <= az ? T(0) : (ay <= az ? T(0) : T(1))};
+        cross3(u, g.a, e);
+        const T il = T(1) / sqrt(dot3(u, u));
+        u[0] *= il; u[1] *= il; u[2] *= il;
+      }
       n[0] = -u[0]; n[1] = -u[1]; n[2] = -u[2];
       dist = -ds - r;
     } else {

@@ -913,6 +913,14 @@ static int sphere_cylinder(const double* c, double r, const Convex* g, double* d
   } else {
     double ds = g->r - rho, dc = g->hh - fabs(z);
     if (ds < dc) { /* exit through the side: the cylinder surface lies outward along u */
+      if (!(rho > 1e-12)) { /* the centre on the axis: any direction across it (bb_bodycon.h) */
+        double ax = fabs(g->a[0]), ay = fabs(g->a[1]), az = fabs(g->a[2]), e[3] = {0, 0, 0};
+        e[ax <= ay && ax <= az ? 0 : (ay <= az ? 1 : 2)] = 1;
+        u[0] = g->a[1] * e[2] - g->a[2] * e[1];
+        u[1] = g->a[2] * e[0] - g->a[0] * e[2];
+        u[2] = g->a[0] * e[1] - g->a[1] * e[0];
+        v3scl(u, u, 1.0 / v3norm(u));
+      }
       for (int k = 0; k < 3; k++) n[k] = -u[k];
       *dist = -ds - r;
     } else {

@@ -12,10 +12,11 @@ A  t16::collide_team against tests/collide_ref.py (the prism as five half-spaces
 B  four very different trip counts in one wave (0 prisms, no hit, one round, many rounds), all live
    and with rows 0b0101: each team's list is bit for bit the one it gives when its state fills all
    four teams, and exited teams write nothing.
-C  t16::collide_body_team against the oracle, fp64.  There is NO independent reference for this
-   part: the capsule / cylinder x prism forms are shared with the oracle (tests/test_host_geometry.py
-   holds one of them to a second formulation).  This pins what the device adds: the two-pass
-   compaction, the order, the per-pair cap of 50 and the LDS / spill split -- not the formulas.
+C  t16::collide_body_team against the oracle, fp64.  The oracle shares the capsule / cylinder x prism
+   forms, so this pins what the team pass adds: the two-pass compaction, the order, the per-pair cap
+   of 50 and the LDS / spill split -- not the formulas.  The formulas have their own independent
+   reference: tests/test_gpu_bodycon.py (device) and tests/test_host_bodycon.py (host build) hold
+   the four primitives of bb_bodycon.h to a Minkowski-hull construction (tests/bodycon_ref.py).
 D  t16::body_candidates is one-sided: "no" only where the oracle has no base-tree contact.  A false
    "no" would silently drop base-tree contacts in the fast kernel.
 
@@ -235,8 +236,8 @@ def _oracle(oracle, q, hf):
 
 def test_base_tree_list_matches_oracle(lib, body_sets):
     """C: collide_body_team per slot against the oracle's base-tree contacts (fp64).  Not an independent
-    reference (see the module docstring): it pins the compaction, the order, the per-pair cap and
-    the LDS / spill split.  dist and pos within 1e-9, the project's bound for the capsule-prism forms
+    reference (the primitives have theirs in test_gpu_bodycon.py): it pins the compaction, the order,
+    the per-pair cap and the LDS / spill split.  dist and pos within 1e-9, the project's bound for the capsule-prism forms
     (test_host_geometry.py; DESIGN §5 measured 1.1e-11); normals within 1e-6 where |dist| >= 1e-3."""
     touched = past = total = 0
     worst = dict(dist=0.0, pos=0.0, normal=0.0)
