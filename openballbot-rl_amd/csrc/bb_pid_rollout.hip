@@ -8,6 +8,17 @@
 #ifndef BB_NO_PRE_BATCH
 #define BB_NO_PRE_BATCH
 #endif
+// for the same reason its solve keeps its operands where they were and its three sums apart
+// (bb_solve.h, bb_team16.h; the same bits either way): no square rows, no workspace growth here
+#ifndef BB_NO_HROW_SQUARE
+#define BB_NO_HROW_SQUARE
+#endif
+#ifndef BB_NO_GROUND_RECORD
+#define BB_NO_GROUND_RECORD
+#endif
+#ifndef BB_NO_SUM3
+#define BB_NO_SUM3
+#endif
 #ifdef BB_PHASE_CLOCKS  // diagnostic builds: this unit's counters under their own name
 #define bb_phase_cycles bb_phase_cycles_pid
 #endif

@@ -149,6 +149,53 @@ struct TerrainRef {
   T size_z, hz;
 };
 
+// -DBB_NO_HROW_SQUARE / -DBB_NO_GROUND_RECORD (A/B builds, tools/build_variant.sh; the serial
+// library has both): where the FUSE kernels' solve (bb_team16.h: solve16<false, true>) finds its
+// operands.  The other kernels keep the earlier places: those at the register limit spill more with
+// the one address than with the fifteen, and bb_pid_rollout.hip's unit turns both off.
+//   kHrowSquare    a lane reads its row of the dense mass matrix from a copy stored by rows (one
+//                  address per lane, the fifteen entries at compile-time offsets from it) instead
+//                  of through hidx from the packed triangle, whose row is fifteen scattered
+//                  addresses (hsq_row_off, t16::mass_rows_team)
+//   kGroundRecord  a ball-terrain contact's Jacobian, aref and D lie in one record (grec_off)
+//                  instead of in two regions
+// Only addresses differ: the same values reach the same operations.
+#ifndef BB_NO_HROW_SQUARE
+constexpr bool kHrowSquare = true;
+#else
+constexpr bool kHrowSquare = false;
+#endif
+#ifndef BB_NO_GROUND_RECORD
+constexpr bool kGroundRecord = true;
+#else
+constexpr bool kGroundRecord = false;
+#endif
+constexpr int GC_LDS = 13;  // ball-terrain contacts with an LDS Jacobian (one contact per lane: 3 + 13 = 16)
+// The square copy: row i is HS entries, element (i, k) at its start + k.  HS is odd, so that rows
+// laid behind one another start an odd count of 8-byte words apart: the sixteen lanes of a team
+// read sixteen different bank pairs.  Rows 0 .. HSQ_H_ROWS - 1 start at W.H, which the packed
+// triangle leaves once the rows are formed from it (the fast kernels' solve reads nothing else of
+// it), and run HX entries past NH: the workspace grows by that much, which is what every kernel's
+// LDS still takes without losing a workgroup per CU (the full 105 do not fit).
+// The last three rows lie in the head of W.g: contacts 0 .. GC_LDS - 1 have been read into their
+// records by then (t16::ground_setup) and the solve rebuilds only contacts from GC_LDS on.  They
+// start HSQ_G_PAD in and HS + 2 apart, which continues the sequence of bank pairs (asserted below).
+constexpr int HS = NV;
+constexpr int HSQ_H_ROWS = 12, HSQ_G_PAD = 2, HSQ_G_STRIDE = HS + 2;
+constexpr int HX = kHrowSquare ? HSQ_H_ROWS * HS - NH : 0;
+static_assert(HS % 2 == 1 && HSQ_H_ROWS * HS >= NH, "square rows: odd stride, the packed triangle inside them");
+static_assert(HSQ_G_PAD + (NV - 1 - HSQ_H_ROWS) * HSQ_G_STRIDE + HS <= GC_LDS * NGF,
+              "the last rows of the square copy do not fit the stored contacts' head of W.g");
+// One record per stored ball-terrain contact: J[3][6], aref[3], D.  The first GREC_BC lie in W.bc
+// (base-tree contacts: the full kernel's only), the others in the mass blocks, which the dense
+// matrix has consumed by then.
+constexpr int GREC = 22, GREC_AREF = 18, GREC_D = 21;
+constexpr int GREC_BC = MAXB_LDS * NBF / GREC;
+static_assert(GREC_BC <= GC_LDS && (GC_LDS - GREC_BC) * GREC <= int(sizeof(Mass<double>) / sizeof(double)),
+              "ground records do not fit W.bc and the mass blocks");
+static_assert(GC_LDS * 18 <= MAXB_LDS * NBF && int(sizeof(Mass<double>) / sizeof(double)) >= GC_LDS * 4,
+              "ground Jacobians do not fit W.bc, or aref/D the mass blocks (-DBB_NO_GROUND_RECORD)");
+
 // Per-env working set of one RK step (LDS on the GPU, one per team).
 // Phase-local buffers share storage in a union to fit 16 envs per CU.
 template <typename T>
@@ -169,7 +216,8 @@ struct EnvWork {
   int dbg_nb;                                // diagnostic build: base-tree contacts summed over the step's forwards
 #endif
   Poses<T> P;                                // body poses for the Jacobian rebuilds
-  T H[NH];                                   // Hessian / Cholesky factor (packed lower); dense M on the GPU
+  T H[NH + HX];                              // Hessian / Cholesky factor (packed lower, NH entries); dense M on
+                                             // the GPU; fast kernels' solve: rows of the square copy (above)
   union U {
     struct {                                 // forward pre-phase
       Kin<T> k;
@@ -183,6 +231,35 @@ struct EnvWork {
     } hes;
   } u;
 };
+
+// Where row i of the square copy starts, and ground record c (c < GC_LDS): in entries of T from
+// the workspace's start, so that a lane holds one address for either (ws_at).
+template <typename T>
+BB_HD constexpr int hsq_row_off(int i) {
+  return i < HSQ_H_ROWS ? int(offsetof(EnvWork<T>, H) / sizeof(T)) + i * HS
+                        : int(offsetof(EnvWork<T>, g) / sizeof(T)) + HSQ_G_PAD + (i - HSQ_H_ROWS) * HSQ_G_STRIDE;
+}
+template <typename T>
+BB_HD constexpr int grec_off(int c) {
+  return c < GREC_BC ? int(offsetof(EnvWork<T>, bc) / sizeof(T)) + c * GREC
+                     : int(offsetof(EnvWork<T>, M) / sizeof(T)) + (c - GREC_BC) * GREC;
+}
+template <typename T>
+BB_HD T* ws_at(EnvWork<T>& W, int off) { return reinterpret_cast<T*>(&W) + off; }
+template <typename T>
+BB_HD const T* ws_at(const EnvWork<T>& W, int off) { return reinterpret_cast<const T*>(&W) + off; }
+// the fifteen rows of doubles start in fifteen different 8-byte words modulo 16: ds_read2_b64
+// serves a team's sixteen lanes (lane 15 reads row 14 with lane 14) from different banks
+constexpr bool hsq_rows_spread() {
+  bool seen[16] = {};
+  for (int i = 0; i < NV; i++) {
+    const int r = hsq_row_off<double>(i) % 16;
+    if (seen[r]) return false;
+    seen[r] = true;
+  }
+  return true;
+}
+static_assert(!kHrowSquare || hsq_rows_spread(), "two rows of the square copy share a bank pair");
 
 // base-tree contact b: the first MAXB_LDS in LDS, the rest in the env's spill block
 template <typename T>

@@ -240,7 +240,10 @@ BB_HD int forward(const ModelT<T>& m, const T* q, const T* v, const T* ctrl, T* 
   // 16-lane DPP-row solve: smooth force and dense M staged in the team's LDS
   t16::mass_dense_team<FUSE && kPreBatchDense>(W, tm.tl);
   team_sync();
-  if constexpr (!BODY) t16::ground_setup(m, W, ng, tm.tl);  // into the mass blocks: after mass_dense_team
+  if constexpr (!BODY) t16::ground_setup<FUSE>(m, W, ng, tm.tl);  // into the mass blocks: after mass_dense_team
+  // the FUSE kernels' rows of the dense matrix, over the packed triangle and the stored contacts' head
+  // of W.g: after ground_setup has read them
+  if constexpr (!BODY && FUSE && kHrowSquare) t16::mass_rows_team(W, tm.tl);
 
 #if defined(BB_PHASE_CLOCKS)
   const unsigned long long s_t0 = clock64();

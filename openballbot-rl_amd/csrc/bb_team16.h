@@ -461,31 +461,40 @@ __device__ __forceinline__ void ls_term(const ModelT<T>& m, const EnvWork<T>& W,
 //   line search    s'M s and s'(M a - qfs) from the rows (team sums, no
 //                  replicated mass products); each contact term from the
 //                  contact pass's jar and the stored Jacobian
-constexpr int GC_LDS = 13;  // ball-terrain contacts with an LDS Jacobian (one contact per lane: 3 + 13 = 16)
-static_assert(GC_LDS * 18 <= MAXB_LDS * NBF, "ground Jacobians do not fit W.bc");
+// (GC_LDS and the stored contacts' layout: bb_solve.h)
 
-// aref[3], D of ground contact c (c < GC_LDS), in the mass-block storage
+// aref[3], D of ground contact c (c < GC_LDS), in the mass-block storage (-DBB_NO_GROUND_RECORD)
 template <typename T>
 __device__ __forceinline__ T* ground_ad(EnvWork<T>& W, int c) {
-  static_assert(sizeof(Mass<T>) >= GC_LDS * 4 * sizeof(T), "ground aref/D do not fit the mass blocks");
   return reinterpret_cast<T*>(&W.M) + 4 * c;
+}
+// where stored contact c's Jacobian starts, and its aref[3], D: one record, or W.bc and the mass blocks
+// (REC: the FUSE kernels with kGroundRecord; the register-limited kernels spill more with the record)
+template <bool REC, typename T>
+__device__ __forceinline__ T* ground_j(EnvWork<T>& W, int c) {
+  return REC ? ws_at(W, grec_off<T>(c)) : W.bc + c * 18;
+}
+template <bool REC, typename T>
+__device__ __forceinline__ T* ground_aref(EnvWork<T>& W, int c, T* j) {
+  return REC ? j + GREC_AREF : ground_ad(W, c);
 }
 
 // lane 3 + c: ground contact c's Jacobian rows, aref and D, once per forward
 // (they depend on the stage state only).  W.P and W.vi must be set, and the
 // mass blocks must be consumed (mass_dense_team) before.
-template <typename T>
+template <bool FUSE = false, typename T>
 __device__ __forceinline__ void ground_setup(const ModelT<T>& m, EnvWork<T>& W, int ng, int tl) {
+  constexpr bool REC = FUSE && kGroundRecord;
   const int c = tl - 3;
   if (c >= 0 && c < ng && c < GC_LDS) {
     T J[3][6], ar[3], D;
     ground_contact(m, W.g + c * NGF, W.P.RB, W.vi, J, ar, D);
-    T* o = W.bc + c * 18;
+    T* o = ground_j<REC>(W, c);
 #pragma unroll
     for (int r = 0; r < 3; r++)
 #pragma unroll
       for (int i = 0; i < 6; i++) o[6 * r + i] = J[r][i];
-    T* ad = ground_ad(W, c);
+    T* ad = ground_aref<REC>(W, c, o);
 #pragma unroll
     for (int r = 0; r < 3; r++) ad[r] = ar[r];
     ad[3] = D;
@@ -494,15 +503,16 @@ __device__ __forceinline__ void ground_setup(const ModelT<T>& m, EnvWork<T>& W, 
 
 // ground contact c's Jacobian, aref and D: stored (fast kernel), or rebuilt
 // past GC_LDS and in the full kernel (its W.bc holds the base-tree contacts)
-template <bool BODY, typename T>
+template <bool BODY, bool FUSE = false, typename T>
 __device__ __forceinline__ void ground_get(const ModelT<T>& m, EnvWork<T>& W, int c, T (&J)[3][6], T (&ar)[3], T& D) {
+  constexpr bool REC = FUSE && kGroundRecord;
   if (!BODY && c < GC_LDS) {
-    const T* o = W.bc + c * 18;
+    const T* o = ground_j<REC>(W, c);
 #pragma unroll
     for (int r = 0; r < 3; r++)
 #pragma unroll
       for (int i = 0; i < 6; i++) J[r][i] = o[6 * r + i];
-    const T* ad = ground_ad(W, c);
+    const T* ad = ground_aref<REC>(W, c, const_cast<T*>(o));
 #pragma unroll
     for (int r = 0; r < 3; r++) ar[r] = ad[r];
     D = ad[3];
@@ -569,6 +579,15 @@ constexpr bool kPrepSelect = true;
 constexpr bool kPrepSelect = false;
 #endif
 
+// -DBB_NO_SUM3 (A/B builds): the FUSE kernels' solve sums s'g, s'M s and s'(M a - qfs) one after
+// the other, as the other kernels do (the register-limited kernels spill with the interleaved
+// form), instead of in one tsum_n behind the sweeps.
+#ifndef BB_NO_SUM3
+constexpr bool kSum3 = true;
+#else
+constexpr bool kSum3 = false;
+#endif
+
 template <bool BODY, bool FUSE = false, typename T>
 __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, int tl) {
   if constexpr (!BODY) nb = 0;
@@ -597,15 +616,23 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
                 "wheel f/C scratch needs wf and hg adjacent");
   T* const wCf = &W.u.hes.wf[0][0];
   const bool gsum = ng > 0;  // team-uniform
+  // this lane's row of the dense mass matrix.  The fast kernels read it from the copy stored by
+  // rows (mass_rows_team; kHrowSquare, bb_solve.h): one address, entry k at offset k, where the
+  // packed triangle's row is fifteen addresses that the compiler parked in AGPRs and read back
+  // before every load.  The FUSE kernels only: the full kernels' W.g and W.H are live, and the
+  // register-limited fast kernels spill more with the one address than with the fifteen.
+  constexpr bool SQ = kHrowSquare && FUSE && !BODY;
+  const T* const hrow = SQ ? ws_at(W, hsq_row_off<T>(row)) : W.H;
+#define BB_HROW_LDS(k) (SQ ? hrow[k] : W.H[hidx(row, k)])
 #ifdef BB_HROW_REG
-  // this lane's row of the dense mass matrix, held in registers across the Newton
-  // iterations (W.H does not change during the solve) instead of re-read from LDS
+  // held in registers across the Newton iterations (it does not change during the solve)
+  // instead of re-read from LDS
   T hM[NV];
 #pragma unroll
-  for (int k = 0; k < NV; k++) hM[k] = W.H[hidx(row, k)];
+  for (int k = 0; k < NV; k++) hM[k] = BB_HROW_LDS(k);
 #define BB_HROW(k) hM[k]
 #else
-#define BB_HROW(k) W.H[hidx(row, k)]
+#define BB_HROW(k) BB_HROW_LDS(k)
 #endif
   PH_DECL
   // carried across the Newton iterations, as in mj_solPrimal: this lane's first-round contact's
@@ -691,7 +718,7 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
           T jar[3] = {jar0[0], jar0[1], jar0[2]}, Dc = 0, Jg[3][6];
           if (!wheel) {
             T ar[3];
-            ground_get<BODY>(m, W, c - 3, Jg, ar, Dc);
+            ground_get<BODY, FUSE>(m, W, c - 3, Jg, ar, Dc);
             if (fresh) {
 #pragma unroll
               for (int r = 0; r < 3; r++) jar[r] = ground_dot(Jg, r, a) - ar[r];
@@ -722,7 +749,7 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
         if (more) {
           for (int c = tl + L; c < ngc; c += L) {
             T jar[3], Dc = 0, Jg[3][6], ar[3];
-            ground_get<BODY>(m, W, c - 3, Jg, ar, Dc);
+            ground_get<BODY, FUSE>(m, W, c - 3, Jg, ar, Dc);
 #pragma unroll
             for (int r = 0; r < 3; r++) jar[r] = ground_dot(Jg, r, a) - ar[r];
             T f[3], Cc[6], w[3][6];
@@ -737,7 +764,7 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
           T jar[3] = {jar0[0], jar0[1], jar0[2]}, Dc = 0, Jg[3][6];  // c == tl: carried
           if (!wheel) {
             T ar[3];
-            ground_get<BODY>(m, W, c - 3, Jg, ar, Dc);
+            ground_get<BODY, FUSE>(m, W, c - 3, Jg, ar, Dc);
             if (fresh || c != tl) {
 #pragma unroll
               for (int r = 0; r < 3; r++) jar[r] = ground_dot(Jg, r, a) - ar[r];
@@ -1082,26 +1109,48 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
 #endif
     static_assert(sizeof(W.u.hes.cj) >= LTR_SLOTS * sizeof(T), "L's transpose and its spare slot do not fit cj");
     chol_solve_rows<FUSE, FUSE>(h, diag, gi, s, sown, tlx, &W.u.hes.cj[0][0][0]);  // cj is dead after the Hessian
-    T d0 = tsum(sown * gi);
+    // s'g, and the line search's s'M s and s'(M a - qfs).  SUM3: all three inputs exist once (M s)_i
+    // is formed, so the three team sums run as one interleaved tsum_n (tsum's bits for each, one
+    // DPP chain's latency instead of three); the fallback below changes s and sums again.
+    constexpr bool SUM3 = FUSE && kSum3;
+    T d0, Ms = 0, sMs = 0, gs = 0;
+    if constexpr (SUM3) {
+#pragma unroll
+      for (int k = 0; k < NV; k++) Ms += BB_HROW(k) * s[k];
+      T p3[3] = {sown * gi, sown * Ms, sown * mq};
+      tsum_n(p3);
+      d0 = p3[0]; sMs = p3[1]; gs = p3[2];
+    } else {
+      d0 = tsum(sown * gi);
+    }
     bool fin = true;
 #pragma unroll
     for (int i = 0; i < NV; i++) fin = fin && isfinite(s[i]);
     if (!fin || !(d0 < 0)) {
       // roundoff-indefinite Hessian: diagonal Newton from this row, then replicated
-      sown = rowl ? -gi / maxT(W.H[hidx(row, row)], T(1e-30)) : T(0);
+      sown = rowl ? -gi / maxT(SQ ? hrow[row] : W.H[hidx(row, row)], T(1e-30)) : T(0);
       static_for<NV>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         s[k] = bcast<k>(sown);
       });
       d0 = tsum(sown * gi);
       if (!(d0 < 0)) break;
+      if constexpr (SUM3) {
+        Ms = 0;
+#pragma unroll
+        for (int k = 0; k < NV; k++) Ms += BB_HROW(k) * s[k];
+        sMs = tsum(sown * Ms);
+        gs = tsum(sown * mq);
+      }
     }
     PH(5)
     // ---- (6) exact line search
-    T Ms = 0;
+    if constexpr (!SUM3) {
 #pragma unroll
-    for (int k = 0; k < NV; k++) Ms += BB_HROW(k) * s[k];
-    const T sMs = tsum(sown * Ms), gs = tsum(sown * mq);
+      for (int k = 0; k < NV; k++) Ms += BB_HROW(k) * s[k];
+      sMs = tsum(sown * Ms);
+      gs = tsum(sown * mq);
+    }
     // this lane's first contact's term from its jar; later rounds rebuild theirs
     LsTerm<T> lt;
     T x[3] = {0, 0, 0};  // J s of the lane's first-round contact
@@ -1121,7 +1170,7 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
         }
       } else if (act) {
         T Jg[3][6], ar[3], D;
-        ground_get<BODY>(m, W, tl - 3, Jg, ar, D);
+        ground_get<BODY, FUSE>(m, W, tl - 3, Jg, ar, D);
 #pragma unroll
         for (int r = 0; r < 3; r++) { x[r] = ground_dot(Jg, r, s); Dc[r] = D; }
       }
@@ -1144,7 +1193,7 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
         }
       } else {
         T Jg[3][6], ar[3], D;
-        ground_get<BODY>(m, W, tl - 3, Jg, ar, D);
+        ground_get<BODY, FUSE>(m, W, tl - 3, Jg, ar, D);
 #pragma unroll
         for (int r = 0; r < 3; r++) { x[r] = ground_dot(Jg, r, s); Dc[r] = D; }
       }
@@ -1279,6 +1328,7 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
   }
   PH(7)
 #undef BB_HROW
+#undef BB_HROW_LDS
   if constexpr (BODY) {
     PH_FLUSH_BODY((Team{L, tl}))
   } else {
@@ -1777,6 +1827,23 @@ __device__ __forceinline__ void mass_dense_team(EnvWork<T>& W, int tl) {
       W.H[e] = mass_entry(W.M, i, j);
     }
   }
+}
+
+// The dense mass matrix by rows for the fast kernels' solve (kHrowSquare, bb_solve.h): lane i
+// reads row i out of the packed triangle (through hidx, once per forward, where the solve read it
+// so twice per Newton iteration) and stores it at hsq_row_off(i); lane 15 copies row 14 with lane
+// 14.  The rows overwrite the triangle and the head of W.g: every lane's loads are issued ahead
+// of the first store (one wave, LDS operations in order), and ground_setup must have run.
+template <typename T>
+__device__ __forceinline__ void mass_rows_team(EnvWork<T>& W, int tl) {
+  const int row = tl < NV ? tl : NV - 1;
+  T x[NV];
+#pragma unroll
+  for (int k = 0; k < NV; k++) x[k] = W.H[hidx(row, k)];
+  BB_ISSUE_FENCE();
+  T* o = ws_at(W, hsq_row_off<T>(row));
+#pragma unroll
+  for (int k = 0; k < NV; k++) o[k] = x[k];
 }
 
 }  // namespace t16

@@ -8,7 +8,10 @@ counts the waits on a just-issued LDS read: an `s_waitcnt lgkmcnt(0)` within
 three instructions after a `ds_read*`.  Two more columns count the exec-mask
 control flow: xbr, the `s_cbranch_exec*` instructions, and short, the bodies of
 at most 45 instructions that an `s_cbranch_execz` skips forward over (the code
-between the branch and its target), attributed to the branch's phase.
+between the branch and its target), attributed to the branch's phase.  The last two,
+agpr-rd and addr-reload, count the `v_accvgpr_read_b32` and those of them whose
+destination is the address operand of a `ds_*` within the next five instructions:
+an LDS address that was parked in an AGPR and is brought back for one access.
 
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DBB_ISA_MARKS -I openballbot-rl_amd/csrc \
       --cuda-device-only -S -o /tmp/bbk.s openballbot-rl_amd/csrc/bb_kernels.hip
@@ -61,6 +64,7 @@ def main(path):
     cur = None
     nins, labels, execz = {}, {}, {}  # per function: instructions so far, label -> index, (phase, index, target)
     since_read = None  # instructions since the last ds_read*, None when there was none in this phase
+    pending, pending_phase = [], None  # (destination, age) of the recent v_accvgpr_read in this phase
     for line in open(path):
         m = re.match(r"^(_Z[^:\s]+):", line)
         if m:
@@ -86,6 +90,20 @@ def main(path):
             continue
         op = s.split()[0]
         counts[func][cur][classify(op)] += 1
+        # AGPR reads, and those of them that bring back an LDS address: the destination is the
+        # address operand of a ds_* within five instructions
+        pending = [(r, n + 1) for r, n in pending if n < 5] if pending_phase == (func, cur) else []
+        pending_phase = (func, cur)
+        ops = [o.strip() for o in s[len(op):].split(";")[0].split(",")]
+        if op.startswith("v_accvgpr_read"):
+            counts[func][cur]["agpr"] += 1
+            pending.append((ops[0], 0))
+        elif op.startswith("ds_") and ops:
+            addr = (ops[0] if op.startswith("ds_write") else ops[1] if len(ops) > 1 else "").split()[0:1]
+            hit = [p for p in pending if addr and p[0] == addr[0]]
+            if hit:
+                counts[func][cur]["areload"] += 1
+                pending.remove(hit[0])
         if op.startswith("s_cbranch_exec"):
             counts[func][cur]["xbr"] += 1
             if op == "s_cbranch_execz":
@@ -116,11 +134,14 @@ def main(path):
             nxt = {10: "contact pass", 0: "ground sums", 1: "gradient", 2: "hessian row", 3: "cholesky", 4: "sweeps",
                    5: "ls setup", 8: "ls loop", 9: "update", 6: "conv test"}[k]
             tot.update(c)
-            print("  after mark %d (%-14s) valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d read-wait %3d xbr %3d short %3d %s" %
+            print("  after mark %d (%-14s) valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d read-wait %3d xbr %3d short %3d "
+                  "agpr-rd %3d addr-reload %3d %s" %
                   (k, nxt, c["valu"], c["dpp"], c["lds"], c["vmem"], c["salu"], c["wait"], c["rwait"], c["xbr"], c["short"],
-                   sorted(bodies.get(func, {}).get(k, []))))
-        print("  total                        valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d read-wait %3d xbr %3d short %3d" %
-              (tot["valu"], tot["dpp"], tot["lds"], tot["vmem"], tot["salu"], tot["wait"], tot["rwait"], tot["xbr"], tot["short"]))
+                   c["agpr"], c["areload"], sorted(bodies.get(func, {}).get(k, []))))
+        print("  total                        valu %5d dpp %4d lds %4d vmem %3d salu %4d wait %4d read-wait %3d xbr %3d short %3d "
+              "agpr-rd %3d addr-reload %3d" %
+              (tot["valu"], tot["dpp"], tot["lds"], tot["vmem"], tot["salu"], tot["wait"], tot["rwait"], tot["xbr"], tot["short"],
+               tot["agpr"], tot["areload"]))
 
 
 PRE_NAMES = {0: "kernel prologue", 1: "stage state", 2: "kinematics", 3: "wheel lanes", 4: "mass_finish",
