@@ -17,7 +17,7 @@ LIB_PATH = PKG / "_lib" / "libbb_mi355x.so"
 SERIAL_LIB_PATH = PKG / "_lib" / "libbb_mi355x_serial.so"
 SERIAL_FLAGS = ["-DBB_NO_TWIN_KIN", "-DBB_NO_TWIN_POS", "-DBB_NO_TWIN_BIAS", "-DBB_NO_MODEL_ONCE",
                 "-DBB_NO_PRE_BATCH", "-DBB_NO_PRISM_WINDOW", "-DBB_NO_HROW_SQUARE", "-DBB_NO_GROUND_RECORD",
-                "-DBB_NO_SUM3"]
+                "-DBB_NO_SUM3", "-DBB_NO_LEAN_SOLVE"]
 CSRC = PKG.parent / "csrc"
 INCLUDE = PKG.parent.parent / "include"
 

@@ -19,6 +19,11 @@
 #ifndef BB_NO_SUM3
 #define BB_NO_SUM3
 #endif
+// and its factorisation and sweeps keep the parent's text (bb_team16.h; the same bits either way):
+// with the lean forms pid_rollout_kernel<double, false> goes from 20 to 28 B of scratch
+#ifndef BB_NO_LEAN_SOLVE
+#define BB_NO_LEAN_SOLVE
+#endif
 #ifdef BB_PHASE_CLOCKS  // diagnostic builds: this unit's counters under their own name
 #define bb_phase_cycles bb_phase_cycles_pid
 #endif

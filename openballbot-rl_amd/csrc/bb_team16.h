@@ -46,6 +46,38 @@ BB_HD int ltr_slot(int tl, int k) {
   return base + k;
 }
 
+// (compiled by the host check too: tests/hostcheck/lean_solve_check.cpp)
+// The lean forms of the factorisation and the sweeps (chol_rows, chol_solve_rows; DESIGN 6, round
+// 15), FUSE kernels only.  ltr_slot's address from one base per lane: lane tl's row of the triangle
+// starts ltr_lane_base(tl) entries into the scratch, so its entry k goes to
+// (k < ltr_rows(tl) ? base + k : LTR_SPARE), a select between two addresses that depend on the
+// lane alone (plus k) instead of an index that is scaled and rebased for every entry.
+BB_HD int ltr_rows(int tl) { return tl < NV ? tl : 0; }
+BB_HD int ltr_lane_base(int tl) { return ltr_rows(tl) * (ltr_rows(tl) - 1) / 2; }
+// (in units of `stride`: entries for the host check, bytes for the kernel's LDS addresses)
+BB_HD unsigned ltr_lane_addr(unsigned row_at, unsigned spare_at, int rows, int k, unsigned stride) {
+  return k < rows ? row_at + stride * unsigned(k) : spare_at;
+}
+BB_HD int ltr_lane_slot(int base, int rows, int k) { return int(ltr_lane_addr(unsigned(base), unsigned(LTR_SPARE), rows, k, 1u)); }
+// the pivot floor of a row from its diagonal before the factorisation (chol_rows)
+template <typename T>
+BB_HD T pivot_floor(T hd) { return pivot_eps<T>() * maxT(hd, T(1e-30)); }
+// x[tl] on lane tl (lane 15: last) through four levels of selects on the bits of tl: fifteen
+// selects and four masks, where `tl == k ? x[k] : ...` takes fifteen masks
+template <typename T>
+BB_HD T lane_pick(const T (&x)[NV], T last, int tl) {
+  const bool b0 = tl & 1, b1 = tl & 2, b2 = tl & 4, b3 = tl & 8;
+  // (values, not elements: a select between two elements of one array becomes an indexed load,
+  // and the array then lives in scratch)
+  const T x0 = x[0], x1 = x[1], x2 = x[2], x3 = x[3], x4 = x[4], x5 = x[5], x6 = x[6], x7 = x[7], x8 = x[8],
+          x9 = x[9], x10 = x[10], x11 = x[11], x12 = x[12], x13 = x[13], x14 = x[14];
+  const T p0 = b0 ? x1 : x0, p1 = b0 ? x3 : x2, p2 = b0 ? x5 : x4, p3 = b0 ? x7 : x6, p4 = b0 ? x9 : x8,
+          p5 = b0 ? x11 : x10, p6 = b0 ? x13 : x12, p7 = b0 ? last : x14;
+  const T q0 = b1 ? p1 : p0, q1 = b1 ? p3 : p2, q2 = b1 ? p5 : p4, q3 = b1 ? p7 : p6;
+  const T r0 = b2 ? q1 : q0, r1 = b2 ? q3 : q2;
+  return b3 ? r1 : r0;
+}
+
 #ifdef __HIP_DEVICE_COMPILE__
 namespace t16 {
 
@@ -295,18 +327,79 @@ __device__ __forceinline__ T rsqrt_piv(T x) {
   }
 }
 
+// -DBB_NO_LEAN_SOLVE (all of them) / _MAX / _FLOOR / _DIAG / _LTR (A/B builds,
+// tools/build_variant.sh; the serial library is built without the set): the FUSE kernels'
+// factorisation and sweeps without work the result does not need.  Operands,
+// operations and their order per result are the parent's, so the bits are.
+//   kLeanMax    the pivot's maximum as one v_max (max1).  fmax() on a value that comes out of a
+//               DPP move or an asm costs a canonicalising v_max x, x first, on the pivot chain
+//   kLeanFloor  the lane's diagonal picked by a four-level select tree over the lane index's bits
+//               (lane_pick: no fifteen lane masks, which the compiler hoists out of the Newton loop
+//               and spills) and its pivot floor formed once, ahead of the columns; the maximum is
+//               taken on the lane's own entry and floor and then broadcast: lane j's operands
+//   kLeanDiag   chol_rows hands the lane its own 1 / L_ii (down) and the sweeps use that: the
+//               forward sweep reads t = b diag[j] from lane j only, the backward sweep's
+//               bcast<i>(z) * diag[i] is bcast<i>(z * down).  diag[] dies with the factorisation
+//               (the backward sweep's step fused into one v_fmac_f64_dpp behind the multiply was
+//               measured too, and the set is 0.9% faster without it: not kept)
+//   kLeanLtr    the transpose's stores from one lane address (ltr_lane_slot)
+//               (the transposed column read without an exec-mask region round each load was
+//               measured as well, and the set is 0.7% faster without it: not kept)
+#if !defined(BB_NO_LEAN_SOLVE) && !defined(BB_NO_LEAN_SOLVE_MAX)
+constexpr bool kLeanMax = true;
+#else
+constexpr bool kLeanMax = false;
+#endif
+#if !defined(BB_NO_LEAN_SOLVE) && !defined(BB_NO_LEAN_SOLVE_FLOOR)
+constexpr bool kLeanFloor = true;
+#else
+constexpr bool kLeanFloor = false;
+#endif
+#if !defined(BB_NO_LEAN_SOLVE) && !defined(BB_NO_LEAN_SOLVE_DIAG)
+constexpr bool kLeanDiag = true;
+#else
+constexpr bool kLeanDiag = false;
+#endif
+#if !defined(BB_NO_LEAN_SOLVE) && !defined(BB_NO_LEAN_SOLVE_LTR)
+constexpr bool kLeanLtr = true;
+#else
+constexpr bool kLeanLtr = false;
+#endif
+
+// max(a, b) as the one hardware instruction.  What fmax(a, b) compiles to when the compiler knows
+// both operands canonical; where it does not (a DPP move's or an asm's result) it puts v_max x, x
+// in front, which changes a signalling NaN alone, and no arithmetic instruction produces one: the
+// operands here are sums and products.  A quiet NaN gives the other operand, as fmax does.
+template <typename T>
+__device__ __forceinline__ T max1(T a, T b) {
+  T r;
+  if constexpr (sizeof(T) == 8) asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  else asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
 // Cholesky of the register-distributed H (lane i holds row h[0..14]); on exit
 // lane i holds L_ik (k < i) in h[k] and every lane holds diag[] = 1 / L_jj.
 // Entries right of a lane's diagonal (the upper triangle) are updated too,
 // without a select: they are never read, by the factorisation or the solves.
+// The lean forms (FUSE): hdi is not read, the lane picks its diagonal itself (kLeanFloor), and
+// down is the lane's own 1 / L_ii (kLeanDiag; lane 15: 0).
 template <bool FUSE = false, typename T>
-__device__ __forceinline__ void chol_rows(T (&h)[NV], T hdi, T (&diag)[NV], int tl) {
+__device__ __forceinline__ void chol_rows(T (&h)[NV], T hdi, T (&diag)[NV], T& down, int tl) {
+  constexpr bool LMAX = FUSE && kLeanMax, LFLOOR = FUSE && kLeanFloor, LDIAG = FUSE && kLeanDiag;
+  T flo = 0;  // this lane's pivot floor
+  if constexpr (LFLOOR) flo = pivot_floor(lane_pick(h, h[NV - 1], tl));
   static_for<NV>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
-    T piv = bcast<j>(h[j]);
-    const T hdj = bcast<j>(hdi);
-    const T fl = pivot_eps<T>() * maxT(hdj, T(1e-30));
-    piv = fmax(piv, fl);  // one v_max on the pivot chain (piv is finite or the direction is rejected)
+    T piv;
+    if constexpr (LFLOOR) {
+      // lane j's maximum of its own entry and floor, broadcast: one v_max on the pivot chain
+      piv = bcast<j>(LMAX ? max1(h[j], flo) : fmax(h[j], flo));
+    } else {
+      piv = bcast<j>(h[j]);
+      const T fl = pivot_floor(bcast<j>(hdi));
+      piv = LMAX ? max1(piv, fl) : fmax(piv, fl);  // (piv is finite or the direction is rejected)
+    }
     const T id = rsqrt_piv(piv);  // 1 / L_jj in one reciprocal square root (no sqrt + divide chain)
     diag[j] = id;  // inverse pivot: the solves multiply
     h[j] *= id;
@@ -320,6 +413,12 @@ __device__ __forceinline__ void chol_rows(T (&h)[NV], T hdi, T (&diag)[NV], int 
       });
     }
   });
+  down = LDIAG ? lane_pick(diag, T(0), tl) : T(0);
+}
+template <bool FUSE = false, typename T>
+__device__ __forceinline__ void chol_rows(T (&h)[NV], T hdi, T (&diag)[NV], int tl) {
+  T down;
+  chol_rows<FUSE>(h, hdi, diag, down, tl);
 }
 
 // s = -(L L')^-1 g with L distributed by rows (lane i: L_i,0..i-1 in h[]);
@@ -331,15 +430,21 @@ __device__ __forceinline__ void chol_rows(T (&h)[NV], T hdi, T (&diag)[NV], int 
 //             (scr: >= NV (NV - 1) / 2 elements of team scratch; SPARE: one more,
 //             LTR_SLOTS): lane k holds column k of L, so s_i needs one broadcast
 //             instead of a team sum
+// The lean forms (FUSE; the switches above chol_rows): down is the lane's own 1 / L_ii from
+// chol_rows and stands for diag[] in both sweeps (kLeanDiag).
 template <bool FUSE = false, bool SPARE = false, typename T>
-__device__ __forceinline__ void chol_solve_rows(const T (&h)[NV], const T (&diag)[NV], T gown, T (&s)[NV], T& sown,
-                                                int tl, T* scr) {
+__device__ __forceinline__ void chol_solve_rows(const T (&h)[NV], const T (&diag)[NV], T down, T gown, T (&s)[NV],
+                                                T& sown, int tl, T* scr) {
+  constexpr bool LDIAG = FUSE && kLeanDiag;
+  constexpr bool LLTR = FUSE && SPARE && kLeanLtr;
+  typedef __attribute__((address_space(3))) T lds_t;
   T b = tl < NV ? -gown : T(0);
   T z = 0;  // y of this lane's row
   static_for<NV>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
     if constexpr (FUSE && kFmacDpp) {
-      const T t = b * diag[j];  // lane j's is y_j (diag is replicated); the other lanes' are not read
+      // lane j's is y_j (diag is replicated, down is lane j's entry of it); the other lanes' are not read
+      const T t = b * (LDIAG ? down : diag[j]);
       z = tl == j ? t : z;
       fnmac_bcast<j>(b, t, h[j]);  // b -= L_ij y_j; rows <= j no longer read their right-hand side
     } else {
@@ -348,11 +453,31 @@ __device__ __forceinline__ void chol_solve_rows(const T (&h)[NV], const T (&diag
       b -= h[j] * yj;  // rows <= j no longer read their right-hand side
     }
   });
+  // byte address of the team scratch in LDS, opaque to the compiler here: what the lean stores
+  // derive from it is formed in this iteration, not held in registers across the step loop.
+  // scr MUST point into LDS for this form (the cast below does not check it, and a generic
+  // pointer elsewhere would compile into wrong addresses): FUSE && SPARE is solve16 of the fast step
+  // and multi-step kernels alone, whose workspace W, cj with it, is the kernel's shared memory
+  unsigned sb = 0;
+  if constexpr (LLTR) {
+    sb = unsigned(size_t((lds_t*)scr));
+    asm volatile("" : "+v"(sb));
+  }
   // strictly lower L, packed by rows (row i at i (i - 1) / 2).  SPARE (a caller whose scratch has
   // the spare slot; solve16 in the fast kernels with registers to spare): every lane
   // stores all fourteen columns, without an exec-mask branch round each store: the address is
   // selected (ltr_slot), an entry that is not below the diagonal goes to the spare slot
-  if constexpr (SPARE) {
+  if constexpr (LLTR) {
+    // one address per lane for its row of the triangle and one for the spare slot; an entry takes
+    // an add, a compare and a select (scaled and rebased index: four)
+    const int rows = ltr_rows(tl);
+    const unsigned al = sb + unsigned(sizeof(T)) * unsigned(ltr_lane_base(tl));
+    const unsigned sp = sb + unsigned(sizeof(T)) * unsigned(LTR_SPARE);
+    static_for<NV - 1>([&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      *(lds_t*)size_t(ltr_lane_addr(al, sp, rows, k, unsigned(sizeof(T)))) = h[k];
+    });
+  } else if constexpr (SPARE) {
     static_for<NV - 1>([&](auto kc) {
       constexpr int k = decltype(kc)::value;
       scr[ltr_slot(tl, k)] = h[k];
@@ -372,12 +497,20 @@ __device__ __forceinline__ void chol_solve_rows(const T (&h)[NV], const T (&diag
   T own = 0;
   static_for<NV>([&](auto ic) {
     constexpr int i = NV - 1 - decltype(ic)::value;
-    const T si = bcast<i>(z) * diag[i];
+    // lane i's z down is s_i (floats keep diag[i]: their broadcast rides in the multiply, a move
+    // behind it would not)
+    const T si = LDIAG && sizeof(T) == 8 ? bcast<i>(z * down) : bcast<i>(z) * diag[i];
     s[i] = si;
     z -= Lc[i] * si;
     own = tl == i ? si : own;
   });
   sown = own;
+}
+template <bool FUSE = false, bool SPARE = false, typename T>
+__device__ __forceinline__ void chol_solve_rows(const T (&h)[NV], const T (&diag)[NV], T gown, T (&s)[NV], T& sown,
+                                                int tl, T* scr) {
+  const T down = FUSE && kLeanDiag ? lane_pick(diag, T(0), tl) : T(0);
+  chol_solve_rows<FUSE, SPARE>(h, diag, down, gown, s, sown, tl, scr);
 }
 
 // stored base-tree contact b into registers: LDS slot or the env's HBM spill
@@ -1087,28 +1220,28 @@ __device__ int solve16(const ModelT<T>& m, EnvWork<T>& W, int ng, int nb, T* a, 
     for (int k = 0; k < NV; k++) hdi = row == k ? h[k] : hdi;
     PH(3)
     // ---- (5) factorise and solve
-    T diag[NV], s[NV], sown;
+    T diag[NV], s[NV], sown, down;  // down: the lane's own 1 / L_ii (the lean forms, chol_rows)
 #ifdef BB_EXP_DUP_CHOL  // timing experiment (tools/lib_bench): the factorisation twice
     {
-      T h2[NV], d2[NV];
+      T h2[NV], d2[NV], dn2;
 #pragma unroll
       for (int k = 0; k < NV; k++) h2[k] = h[k];
-      chol_rows<FUSE>(h2, hdi, d2, tl);
-      asm volatile("" :: "v"(d2[NV - 1]), "v"(h2[NV - 2]) : "memory");
+      chol_rows<FUSE>(h2, hdi, d2, dn2, tlx);
+      asm volatile("" :: "v"(d2[NV - 1]), "v"(h2[NV - 2]), "v"(dn2) : "memory");
     }
 #endif
-    chol_rows<FUSE>(h, hdi, diag, tl);
+    chol_rows<FUSE>(h, hdi, diag, down, tlx);
     PH(4)
 #ifdef BB_EXP_DUP_TRSV  // timing experiment: the two triangular sweeps twice
     {
       T s2[NV], so2;
-      chol_solve_rows<FUSE, FUSE>(h, diag, gi, s2, so2, tl, &W.u.hes.cj[0][0][0]);
+      chol_solve_rows<FUSE, FUSE>(h, diag, down, gi, s2, so2, tl, &W.u.hes.cj[0][0][0]);
       asm volatile("" :: "v"(s2[0]), "v"(so2) : "memory");
       team_sync();
     }
 #endif
     static_assert(sizeof(W.u.hes.cj) >= LTR_SLOTS * sizeof(T), "L's transpose and its spare slot do not fit cj");
-    chol_solve_rows<FUSE, FUSE>(h, diag, gi, s, sown, tlx, &W.u.hes.cj[0][0][0]);  // cj is dead after the Hessian
+    chol_solve_rows<FUSE, FUSE>(h, diag, down, gi, s, sown, tlx, &W.u.hes.cj[0][0][0]);  // cj is dead after the Hessian
     // s'g, and the line search's s'M s and s'(M a - qfs).  SUM3: all three inputs exist once (M s)_i
     // is formed, so the three team sums run as one interleaved tsum_n (tsum's bits for each, one
     // DPP chain's latency instead of three); the fallback below changes s and sums again.
