@@ -31,6 +31,7 @@
  *   bb_pid_rollout   the install check's loop (PID.act + env.step) in one launch   scripts/test_pid.py:38-65
  *   bb_eval_track    SB3 evaluate_policy's episode accounting (EvalCallback) + the policy's per-step staging
  *   bb_depth_encoder frozen rgbd encoder of the camera policy, fused
+ *   bb_rgbd_encoder  the same encoder over 4-plane RGB-D frames
  *   bb_gae           SB3 RolloutBuffer.compute_returns_and_advantage (PPO)
  *   bb_forward       mujoco.mj_forward (diagnostic)             ballbot_env.py:525,620
  *   bb_get_state/    read/write qpos/qvel/qacc_warmstart        ballbot_env.py:616-617
@@ -475,6 +476,20 @@ int bb_depth_encoder_workspace_bytes(int64_t n, int64_t* bytes);
 int bb_depth_encoder(const bb_encoder_params* params, const float* images_dev, int64_t image_stride,
                      const int64_t* index_dev, int64_t n, int height, int width, int train, float momentum, float eps,
                      float* out_dev, int64_t out_stride, float* workspace_dev, int64_t workspace_bytes, void* stream);
+/* The same encoder for RGB-D frames (camera.disable_rgb: false): Conv2d(4,32,3,s2,p1) first, so
+ * params->conv1_w is [32][4][3][3]; every other tensor, the train / eval semantics, index_dev, the
+ * skip rule of a negative entry and its train-mode check are bb_depth_encoder's.  An image is four
+ * contiguous 64x64 planes R, G, B, D at images_dev + j * image_stride floats (16-byte aligned,
+ * image_stride >= 16384 and a multiple of 4): a camera slice of bb_render_rgbd's output is one
+ * (image_stride = n_cameras * 16384, offset camera * 16384).  channels must be 4 (bb_depth_encoder
+ * encodes 1), height and width 64.  Its workspace has its own size.  Six launches in train mode,
+ * five in eval mode; graph-capturable; no allocation, memset or host read apart from that index
+ * check.  Present from the library that exports the symbol; BB_ABI_VERSION is unchanged. */
+int bb_rgbd_encoder_workspace_bytes(int64_t n, int64_t* bytes);
+int bb_rgbd_encoder(const bb_encoder_params* params, const float* images_dev, int64_t image_stride,
+                    const int64_t* index_dev, int64_t n, int channels, int height, int width, int train,
+                    float momentum, float eps, float* out_dev, int64_t out_stride, float* workspace_dev,
+                    int64_t workspace_bytes, void* stream);
 /* One evaluation step's bookkeeping on the device (SB3 evaluate_policy over a Monitor-wrapped
  * VecEnv, as the reference's EvalCallback calls it, ballbot_rl/training/callbacks.py:607-617): the
  * episode accounting, and the per-step staging of the policy's input.  No handle.

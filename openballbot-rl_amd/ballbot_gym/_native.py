@@ -161,7 +161,7 @@ EXPORTS = [
     "bb_set_terrain_stream", "bb_get_env_terrain", "bb_kernel_times", "bb_step_multi", "bb_rollout",
     "bb_set_terrain_rng", "bb_get_terrain_rng", "bb_pair_counters", "bb_pair_env_times", "bb_check",
     "bb_reward_terms", "bb_default_view", "bb_render_view", "bb_render_rgbd", "bb_pid_act",
-    "bb_pid_rollout", "bb_eval_track",
+    "bb_pid_rollout", "bb_eval_track", "bb_rgbd_encoder_workspace_bytes", "bb_rgbd_encoder",
 ]
 
 ABI_VERSION = 21  # include/ballbot_mi355x.h BB_ABI_VERSION
@@ -170,8 +170,8 @@ _lib = None
 
 
 HIP_SOURCES = ("bb_kernels.hip", "bb_pair.hip", "bb_terrain.hip", "bb_rollout.hip", "bb_render.hip", "bb_view.hip",
-               "bb_rgbd.hip", "bb_ppo.hip", "bb_mlp.hip", "bb_encoder.hip", "bb_episode_log.hip", "bb_pid.hip",
-               "bb_pid_rollout.hip", "bb_eval.hip")
+               "bb_rgbd.hip", "bb_ppo.hip", "bb_mlp.hip", "bb_encoder.hip", "bb_encoder_rgbd.hip", "bb_episode_log.hip",
+               "bb_pid.hip", "bb_pid_rollout.hip", "bb_eval.hip")
 # per-source flags: the relief pair's unit without MachineLICM (bb_kernels.hip: bb_pair_launch_tu)
 SOURCE_FLAGS = {"bb_pair.hip": ["-mllvm", "-disable-machine-licm"]}
 
@@ -292,9 +292,15 @@ def _load(path: Path):
     L.bb_depth_encoder_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_int64)]
     L.bb_depth_encoder.argtypes = [C.POINTER(EncoderParams), vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int,
                                    C.c_float, C.c_float, vp, C.c_int64, vp, C.c_int64, vp]
+    if hasattr(L, "bb_rgbd_encoder"):  # additive within ABI 21: a library from before it loads, without it
+        L.bb_rgbd_encoder_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_int64)]
+        L.bb_rgbd_encoder.argtypes = [C.POINTER(EncoderParams), vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_float, C.c_float, vp, C.c_int64, vp, C.c_int64, vp]
     L.bb_kernel_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.bb_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     for name in [n for n in EXPORTS if n not in ("bb_default_params", "bb_default_view", "bb_abi_version")]:
+        if name.startswith("bb_rgbd_encoder") and not hasattr(L, name):
+            continue
         getattr(L, name).restype = C.c_int
     if L.bb_abi_version() != ABI_VERSION:
         raise NativeLibraryError("ABI version mismatch")

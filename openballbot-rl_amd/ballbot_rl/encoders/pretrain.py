@@ -8,8 +8,10 @@ envs that log their camera images to disk, loads them into a Dataset, splits
 straight from the GPU env's depth cameras (bb_render_depth, every rendered
 frame of every env, both cameras) into one device tensor, and the training
 loop runs over device-resident minibatches -- no files, no DataLoader workers.
+With --rgbd the env renders RGB-D frames (camera.disable_rgb: false, bb_render_rgbd)
+and a 4-channel autoencoder is trained on them: the frozen encoder of an RGB-D policy.
 
-    python -m ballbot_rl.encoders.pretrain --n_envs 1024 --n_frames 200000 \\
+    python -m ballbot_rl.encoders.pretrain --n_envs 1024 --n_frames 200000 [--rgbd] \\
         --save_encoder_to outputs/encoders/encoder.safetensors [--policy model.safetensors]
 """
 from __future__ import annotations
@@ -24,14 +26,26 @@ from ballbot_rl.encoders.models import TinyAutoencoder, save_encoder
 
 @torch.no_grad()
 def collect_depth_images(env, n_frames: int, policy=None, seed: int = 0, max_steps: int = 100000) -> torch.Tensor:
-    """Depth frames [n_frames, 1, H, W] from the env's cameras (of an RGB-D env: the D planes; the
-    autoencoder is depth-only, as the reference's, encoders/models.py:14).
+    """Depth frames [n_frames, 1, H, W] from the env's cameras (of an RGB-D env: the D planes;
+    collect_camera_images keeps all four).
 
     Each step keeps the images of the envs whose cameras rendered in it
     (the reference's 6-step cadence); actions come from `policy.predict`
     (deterministic, as data/collect.py:31-33) or uniform random in [-1, 1]."""
+    return _collect(env, n_frames, policy, seed, max_steps, depth_only=True)
+
+
+@torch.no_grad()
+def collect_camera_images(env, n_frames: int, policy=None, seed: int = 0, max_steps: int = 100000) -> torch.Tensor:
+    """Camera frames [n_frames, C, H, W] with C = env.cam_channels: depth frames of a depth env,
+    R, G, B, D frames of an RGB-D env (camera.disable_rgb: false).  Cadence and actions as
+    collect_depth_images."""
+    return _collect(env, n_frames, policy, seed, max_steps, depth_only=False)
+
+
+def _collect(env, n_frames, policy, seed, max_steps, depth_only):
     if not getattr(env, "cameras", False):
-        raise ValueError("collect_depth_images needs BallbotVecEnv(..., disable_cameras=False)")
+        raise ValueError("collecting camera images needs BallbotVecEnv(..., disable_cameras=False)")
     g = torch.Generator(device=env.device).manual_seed(int(seed))
     obs, _ = env.reset()
     out = []
@@ -40,7 +54,10 @@ def collect_depth_images(env, n_frames: int, policy=None, seed: int = 0, max_ste
     fresh = torch.ones(env.num_envs, dtype=torch.bool, device=env.device)  # reset frames
     for _ in range(max_steps):
         if fresh.any():
-            imgs = env.depth[fresh].reshape(-1, 1, env.cam_h, env.cam_w)
+            if depth_only or env.cam_channels == 1:
+                imgs = env.depth[fresh].reshape(-1, 1, env.cam_h, env.cam_w)
+            else:
+                imgs = env.rgbd[fresh].reshape(-1, env.cam_channels, env.cam_h, env.cam_w)
             out.append(imgs.clone())
             have += imgs.shape[0]
             if have >= n_frames:
@@ -107,7 +124,7 @@ def train_autoencoder(model: TinyAutoencoder, images: torch.Tensor, epochs: int 
 
 
 def cli_main() -> None:
-    ap = argparse.ArgumentParser(description="Pretrain the depth encoder on GPU-rendered frames")
+    ap = argparse.ArgumentParser(description="Pretrain the depth (or, with --rgbd, RGB-D) encoder on GPU-rendered frames")
     ap.add_argument("--n_envs", type=int, default=1024)
     ap.add_argument("--n_frames", type=int, default=100000)
     ap.add_argument("--terrain", default="perlin")
@@ -116,11 +133,14 @@ def cli_main() -> None:
     ap.add_argument("--epochs", type=int, default=100)
     ap.add_argument("--batch_size", type=int, default=64)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--rgbd", action="store_true",
+                    help="render RGB-D frames (camera.disable_rgb: false) and train a 4-channel encoder")
     a = ap.parse_args()
     from ballbot_gym.envs import BallbotVecEnv
 
     env = BallbotVecEnv(a.n_envs, device="cuda:0", terrain_config={"type": a.terrain, "config": {}},
-                        disable_cameras=False, seed=a.seed)
+                        disable_cameras=False, seed=a.seed,
+                        **({"env_config": {"camera": {"disable_rgb": False}}} if a.rgbd else {}))
     policy = None
     if a.policy:
         from safetensors.torch import load_file
@@ -133,9 +153,9 @@ def cli_main() -> None:
                                               width=env.cam_w)).to("cuda:0")
         policy.load_state_dict(sd)
         policy.eval()
-    imgs = collect_depth_images(env, a.n_frames, policy=policy, seed=a.seed)
-    print(f"collected {imgs.shape[0]} depth frames")
-    train_autoencoder(TinyAutoencoder(env.cam_h, env.cam_w), imgs, epochs=a.epochs, batch_size=a.batch_size,
+    imgs = collect_camera_images(env, a.n_frames, policy=policy, seed=a.seed)
+    print(f"collected {imgs.shape[0]} {'RGB-D' if env.cam_channels == 4 else 'depth'} frames")
+    train_autoencoder(TinyAutoencoder(env.cam_h, env.cam_w, in_c=env.cam_channels), imgs, epochs=a.epochs, batch_size=a.batch_size,
                       save_path=a.save_encoder_to, seed=a.seed)
     env.close()
 

@@ -7,7 +7,7 @@
 .safetensors.  The env is the eval env train.py builds: from --config (a run's config.yaml, or a
 training YAML that names its env_config) N = evaluation.num_envs or num_envs envs, env i drawing its
 terrains from np_random(seed + num_envs + i); or, without a config, from the flags (directional
-reward, cameras on when the policy reads 56 features).  --n-envs, --n-episodes, --terrain and
+reward, cameras on when the policy reads 56 features, RGB-D frames when its encoders read 4 channels).  --n-envs, --n-episodes, --terrain and
 --seed override the config.  The fused device-side evaluator runs unless --eager is given; --poll P is
 its host check interval.  Also: --max-steps (the evaluation's step limit), --precision fp32|fp64 (the
 env's arithmetic, fp64 as train.py's default), --device (cuda:0), --out FILE (the JSON line, also written there).
@@ -37,13 +37,13 @@ def _load_policy(path: str, device):
         return load_sb3_policy(path, device)
     from safetensors.torch import load_file
 
-    from ballbot_rl.evaluation.sb3_zip import _empty_policy
+    from ballbot_rl.evaluation.sb3_zip import _empty_policy, encoder_channels
 
     state = load_file(path, device="cpu")
     w0 = state.get("policy_net.0.weight")
     if w0 is None or w0.dim() != 2 or int(w0.shape[1]) not in (15, 56):
         raise ValueError(f"{path}: no 15- or 56-wide policy_net.0.weight: not a policy this tool evaluates")
-    policy = _empty_policy(int(w0.shape[1]))
+    policy = _empty_policy(int(w0.shape[1]), encoder_channels(state) if int(w0.shape[1]) == 56 else 1)
     policy.load_state_dict(state)
     for m in policy.features_extractor.extractors.values():
         m.eval()
@@ -87,7 +87,8 @@ def main(argv=None) -> int:
         problem["reward"] = {"type": "directional", "config": {"target_direction": [0.0, 1.0]}}
     cfg["problem"] = problem
     if cameras and not cfg.get("camera"):
-        cfg["camera"] = {"height": 64, "width": 64, "frame_rate": 90, "disable_rgb": True}
+        rgbd = int(policy.features_extractor.extractors["rgbd_0"][0].in_channels) == 4
+        cfg["camera"] = {"height": 64, "width": 64, "frame_rate": 90, "disable_rgb": not rgbd}
     if not cameras:
         cfg["disable_cameras"] = True
     ev = cfg.get("evaluation", {}) or {}

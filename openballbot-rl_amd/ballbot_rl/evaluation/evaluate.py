@@ -104,7 +104,8 @@ def _ptr(t):
 class DeviceEvaluator:
     """evaluate_policy with the whole step on the device: one captured graph per evaluation step.
 
-    The graph, in order (camera policy): bb_depth_encoder of camera 0 and of camera 1, each masked
+    The graph, in order (camera policy): bb_depth_encoder (depth frames) or bb_rgbd_encoder (RGB-D
+    frames, camera.disable_rgb: false, with 4-channel encoders) of camera 0 and of camera 1, each masked
     by `fresh` (the envs whose cameras rendered in the step before) and writing its 20 columns of
     the feature buffer in place; bb_ppo_mlp_act without noise (the mean, clipped to [-1, 1]); the
     env's step launch (bb_step and the cameras' cadence); bb_eval_track (the episode accounting, the
@@ -118,8 +119,9 @@ class DeviceEvaluator:
     tensors are read in place.  A different n_eval_episodes captures a new graph.
 
     Refused, with a ValueError: a policy that is not the reference's MLP (pi = vf = [128]*4
-    LeakyReLU(0.01), 15 or 56 features), camera encoders bb_depth_encoder does not compute, RGB-D
-    (4-channel) cameras, a host reward plugin, an env that records per-episode logs, an env without
+    LeakyReLU(0.01), 15 or 56 features), camera encoders the fused kernels do not compute, encoders
+    that read another channel count than the env renders (a depth policy on RGB-D frames or the
+    reverse), a host reward plugin, an env that records per-episode logs, an env without
     auto-reset, a sampled (non-deterministic) evaluation."""
 
     def __init__(self, policy, env):
@@ -144,11 +146,9 @@ class DeviceEvaluator:
         if getattr(env, "_log_on", False):
             raise ValueError("the fused evaluator does not step an env that records per-episode logs (log_options): "
                              "the reference's eval env writes none (use fused=False)")
-        if self.cameras and int(getattr(env, "cam_channels", 1)) == 4:
-            raise ValueError("the fused evaluator reads depth cameras: this env renders 4-channel RGB-D frames "
-                             "(camera.disable_rgb: false), which bb_depth_encoder does not encode (use fused=False)")
+        self.channels = int(getattr(env, "cam_channels", 1)) if self.cameras else 0
         if self.cameras and (env.cam_h, env.cam_w) != (64, 64):
-            raise ValueError(f"the fused evaluator needs 64x64 depth frames (got {env.cam_h}x{env.cam_w})")
+            raise ValueError(f"the fused evaluator needs 64x64 camera frames (got {env.cam_h}x{env.cam_w})")
         ext = getattr(policy, "features_extractor", None)
         fd = int(getattr(ext, "features_dim", -1))
         if fd != (56 if self.cameras else 15):
@@ -164,6 +164,15 @@ class DeviceEvaluator:
                     raise ValueError(f"the fused evaluator needs frozen encoders of the reference's layout "
                                      f"(fusable_encoder): features_extractor.extractors.{key} is not one")
             self.encs = (mods["rgbd_0"], mods["rgbd_1"])
+            for key, enc in zip(("rgbd_0", "rgbd_1"), self.encs):
+                want = int(enc[0].in_channels)
+                if want != self.channels:
+                    kind = {1: "depth-only", 4: "RGB-D"}
+                    raise ValueError(f"features_extractor.extractors.{key} reads {want}-channel ({kind[want]}) images, "
+                                     f"this env renders {self.channels}-channel ({kind.get(self.channels, '?')}) frames "
+                                     f"(camera.disable_rgb: {'false' if self.channels == 4 else 'true'}): RGB-D frames "
+                                     "need encoders pretrained on RGB-D frames (pretrain --rgbd), depth frames depth "
+                                     "encoders")
         self.tensors = reference_mlp_tensors(policy, self.cameras)
         if self.tensors is None:
             raise ValueError("the fused evaluator runs the reference's MLP policy (pi = vf = [128]*4 LeakyReLU(0.01), "
@@ -180,9 +189,10 @@ class DeviceEvaluator:
         self.fresh = torch.full((n,), -1, dtype=torch.int64, device=dev) if self.cameras else None
         self.ws = None
         if self.cameras:
-            nbytes = C.c_int64()
-            N.check(N.lib().bb_depth_encoder_workspace_bytes(n, C.byref(nbytes)), "bb_depth_encoder_workspace_bytes")
-            self.ws = torch.empty(int(nbytes.value) // 4 + 4, **f32)  # one scratch: the two encoders run in turn
+            from ballbot_rl.encoders.models import encoder_workspace_bytes
+
+            # one scratch: the two encoders run in turn
+            self.ws = torch.empty(encoder_workspace_bytes(n, self.channels) // 4 + 4, **f32)
         self.ep_ret = torch.zeros(n, dtype=torch.float64, device=dev)
         self.ep_len = torch.zeros(n, dtype=torch.int64, device=dev)
         self.counts = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -215,9 +225,11 @@ class DeviceEvaluator:
 
     def _encode(self, masked: bool) -> None:
         from ballbot_rl.encoders.models import fused_encoder_forward
+        from ballbot_rl.training.ppo import camera_images, env_images
 
+        frames = env_images(self.env)
         for c, enc in enumerate(self.encs):
-            fused_encoder_forward(enc, self.env.depth[:, c:c + 1], index=self.fresh if masked else None,
+            fused_encoder_forward(enc, camera_images(frames, c), index=self.fresh if masked else None,
                                   out=self.feats[:, 13 + 20 * c:33 + 20 * c], out_stride=56, workspace=self.ws)
 
     def _act(self) -> None:

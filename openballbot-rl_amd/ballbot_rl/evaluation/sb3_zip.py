@@ -19,7 +19,9 @@ Key map (SB3 MultiInputPolicy as the reference builds it, train.py:39-56 -> Acto
                                                      shared extractor): must equal it bit for bit
 The observation space follows from the first trunk layer's input width: 15 = the proprio keys,
 56 = proprio + relative_image_timestamp + 2 x 20 camera features.  The encoders come from the zip
-(their BatchNorm statistics moved during training), frozen and in eval mode.
+(their BatchNorm statistics moved during training), frozen and in eval mode.  Their input
+channels follow from features_extractor.extractors.rgbd_0.0.weight: 1 (depth frames) or 4 (RGB-D
+frames, camera.disable_rgb: false).
 """
 from __future__ import annotations
 
@@ -110,14 +112,31 @@ def _to_project(sd: Dict[str, torch.Tensor], meta: Dict[str, object]) -> Tuple["
     return out, width
 
 
-def _empty_policy(width: int):
+_CONV1 = _FE + "extractors.rgbd_0.0.weight"
+
+
+def encoder_channels(state: Dict[str, torch.Tensor]) -> int:
+    """Input channels of a camera policy's encoders, from the first conv's weight [32, C, 3, 3] in a
+    state dict (SB3's names or this project's: the key is the same): 1 or 4; 1 when the key is
+    absent (the key check names it as missing afterwards)."""
+    w = state.get(_CONV1)
+    if w is None:
+        return 1
+    c = int(w.shape[1]) if w.dim() == 4 else -1
+    if c not in (1, 4):
+        raise ValueError(f"{_CONV1!r} has shape {tuple(w.shape)}: the encoders read 1 (depth) or 4 (RGB-D) channels")
+    return c
+
+
+def _empty_policy(width: int, channels: int = 1):
     from ballbot_rl.encoders.models import TinyAutoencoder
     from ballbot_rl.policies.mlp_policy import ActorCriticPolicy, obs_spaces
 
     if width == 15:
         return ActorCriticPolicy(obs_spaces(), 3, ortho_init=False)
-    enc = TinyAutoencoder(64, 64).encoder  # depth_cnn's layout; the Extractor copies it per camera, frozen
-    return ActorCriticPolicy(obs_spaces(cameras=True), 3, frozen_encoder=enc, ortho_init=False)
+    # depth_cnn's layout (4 input planes for RGB-D frames); the Extractor copies it per camera, frozen
+    enc = TinyAutoencoder(64, 64, in_c=channels).encoder
+    return ActorCriticPolicy(obs_spaces(cameras=True, channels=channels), 3, frozen_encoder=enc, ortho_init=False)
 
 
 def _check_keys(state: Dict[str, torch.Tensor], want: Dict[str, torch.Tensor], back=lambda k: k) -> None:
@@ -144,7 +163,7 @@ def policy_state_from_sb3(sd: Dict[str, torch.Tensor], meta: Dict[str, object], 
     fresh policy of the width the zip implies) -> (state, policy)."""
     state, width = _to_project(sd, meta)
     if policy is None:
-        policy = _empty_policy(width)
+        policy = _empty_policy(width, encoder_channels(state) if width == 56 else 1)
     _check_keys(state, policy.state_dict(), _sb3_name)
     return state, policy
 

@@ -89,7 +89,8 @@ class Extractor(nn.Module):
         self.keys = list(observation_space.keys())
         self.features_dim = total
         self._proprio_only = all(k in PROPRIO_KEYS for k in self.keys)
-        # frozen encoders of the reference's layout run as bb_depth_encoder on the GPU
+        # frozen encoders of the reference's layout run as bb_depth_encoder (1 channel) or
+        # bb_rgbd_encoder (4 channels) on the GPU
         self._frozen_keys = set()
         if frozen_encoder is not None:
             from ballbot_rl.encoders.models import fusable_encoder

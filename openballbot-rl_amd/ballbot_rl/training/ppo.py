@@ -175,6 +175,13 @@ def image_shape(env) -> tuple:
     return (2, env.cam_h, env.cam_w) if c == 1 else (2, c, env.cam_h, env.cam_w)
 
 
+def camera_images(frames: torch.Tensor, c: int) -> torch.Tensor:
+    """Camera c's images as its fused frozen encoder reads them, a view of the frame tensor
+    (env_images, a rollout-buffer step or the flattened buffer): [B, 1, H, W] of depth frames
+    [B, 2, H, W], the camera's four planes [B, 4, H, W] of RGB-D frames [B, 2, 4, H, W]."""
+    return frames[:, c] if frames.dim() == 5 else frames[:, c:c + 1]
+
+
 def policy_obs(obs15: torch.Tensor, depth: Optional[torch.Tensor] = None,
                rel_ts: Optional[torch.Tensor] = None):
     """The policy's observation: the packed proprio tensor, or with cameras the
@@ -434,7 +441,7 @@ class _UpdateGraphs:
                 f[:, 12].copy_(d["rel_ts"][idx])            # relative_image_timestamp
                 for c, key in enumerate(("rgbd_0", "rgbd_1")):
                     f[:, 13 + 20 * c:33 + 20 * c].copy_(
-                        fused_encoder_forward(ext.extractors[key], d["depth"][:, c:c + 1], index=idx))
+                        fused_encoder_forward(ext.extractors[key], camera_images(d["depth"], c), index=idx))
                 f[:, 53:56].copy_(o15[:, 12:15])            # vel
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             if not self.dp:
@@ -524,7 +531,7 @@ class _UpdateGraphs:
 
             ext = ppo.policy.features_extractor
             for c, key in enumerate(("rgbd_0", "rgbd_1")):
-                fused_encoder_forward(ext.extractors[key], d["depth"][:, c:c + 1], index=idx)
+                fused_encoder_forward(ext.extractors[key], camera_images(d["depth"], c), index=idx)
         else:
             ppo.policy.features_extractor(ppo._mb_obs(d, idx))
 
@@ -798,10 +805,10 @@ class BatchedPPO:
             idx = None if (t == 0 or not cache) else torch.nonzero(b.rel_ts[t] == 0).view(-1)
             if idx is None:
                 for c, enc in enumerate(encs):
-                    feats[:, 13 + 20 * c:33 + 20 * c].copy_(fused_encoder_forward(enc, b.depth[t][:, c:c + 1]))
+                    feats[:, 13 + 20 * c:33 + 20 * c].copy_(fused_encoder_forward(enc, camera_images(b.depth[t], c)))
             elif idx.numel():
                 for c, enc in enumerate(encs):
-                    f = fused_encoder_forward(enc, b.depth[t][:, c:c + 1], index=idx)
+                    f = fused_encoder_forward(enc, camera_images(b.depth[t], c), index=idx)
                     feats[:, 13 + 20 * c:33 + 20 * c].index_copy_(0, idx, f)
             N.check(lib.bb_ppo_mlp_act(flat, offs, nflat, _ptr(feats), int(feats.shape[1]), _ptr(noise[t]), n, None,
                                        _ptr(b.actions[t]), _ptr(clipped), _ptr(b.values[t]), _ptr(b.log_probs[t]),

@@ -14,8 +14,11 @@ seed, evaluation.*, env.*, problem.terrain/reward).  Differences, by design:
   .zip, of which policy.pth alone is read, weights only); `evaluation.fused: true` runs the
   EvalCallback's evaluations on the device (ballbot_rl.evaluation.DeviceEvaluator); with a `camera` section the
   cameras are on, as in the reference (depth frames, or RGB-D frames and 4-channel
-  CNN branches with `camera.disable_rgb: false`); `frozen_cnn` names a depth encoder
-  pretrained by ballbot_rl.encoders.pretrain (safetensors) -- the reference's
+  CNN branches with `camera.disable_rgb: false`); `frozen_cnn` names an encoder
+  pretrained by ballbot_rl.encoders.pretrain (safetensors; a depth encoder, or with
+  `camera.disable_rgb: false` a 4-channel one from `pretrain --rgbd`: both run as fused HIP
+  kernels in the rollout and the update, and an encoder whose channels are not the env's
+  raises the Extractor's "Channel mismatch") -- the reference's
   pickled encoder files are never loaded -- else the rgbd
   branches are the Extractor's trainable CNNs;
 * the `visualization` section's videos (record_videos, video_freq, video_episodes,

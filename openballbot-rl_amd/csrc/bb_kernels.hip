@@ -45,6 +45,7 @@
 #include "bb_ppo.h"
 #include "bb_mlp.h"
 #include "bb_encoder.h"
+#include "bb_encoder_rgbd.h"
 #include "bb_eval.h"
 #include "bb_pairmap.h"
 
@@ -3061,6 +3062,59 @@ int bb_depth_encoder(const bb_encoder_params* p, const float* images, int64_t im
   a.momentum = momentum; a.eps = eps; a.out = out; a.out_stride = out_stride;
   if (launch_encoder(a, ws, (hipStream_t)stream))
     return fail("bb_depth_encoder: launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return 0;
+}
+
+int bb_rgbd_encoder_workspace_bytes(int64_t n, int64_t* bytes) {
+  if (!bytes) return fail("bb_rgbd_encoder_workspace_bytes: NULL argument");
+  if (n < 0) return fail("bb_rgbd_encoder_workspace_bytes: n must be >= 0");
+  *bytes = rgbd_encoder_workspace_bytes(n);
+  return 0;
+}
+
+int bb_rgbd_encoder(const bb_encoder_params* p, const float* images, int64_t image_stride, const int64_t* index,
+                     int64_t n, int channels, int height, int width, int train, float momentum, float eps, float* out,
+                     int64_t out_stride, float* ws, int64_t ws_bytes, void* stream) {
+  if (!p || !images || !out || !ws) return fail("bb_rgbd_encoder: NULL argument");
+  if (!p->conv1_w || !p->conv1_b || !p->bn1_w || !p->bn1_b || !p->bn1_mean || !p->bn1_var || !p->conv2_w ||
+      !p->conv2_b || !p->bn2_w || !p->bn2_b || !p->bn2_mean || !p->bn2_var || !p->fc_w || !p->fc_b || !p->bn3_w ||
+      !p->bn3_b || !p->bn3_mean || !p->bn3_var)
+    return fail("bb_rgbd_encoder: NULL parameter pointer");
+  if (channels != 4)
+    return fail("bb_rgbd_encoder: only 4-channel (R, G, B, D) images (got %d; bb_depth_encoder encodes 1)", channels);
+  if (height != 64 || width != 64) return fail("bb_rgbd_encoder: only 64x64 images (got %dx%d)", height, width);
+  if (n < 0 || (train && n < 2)) return fail("bb_rgbd_encoder: need n >= 2 in train mode (got %lld)", (long long)n);
+  if ((reinterpret_cast<uintptr_t>(images) & 15) || image_stride % 4 || image_stride < 4 * 64 * 64)
+    return fail("bb_rgbd_encoder: images must be 16-byte aligned with a stride of >= 16384 floats, a multiple of 4");
+  if (out_stride < 20) return fail("bb_rgbd_encoder: out_stride must be >= 20");
+  if (ws_bytes < rgbd_encoder_workspace_bytes(n))
+    return fail("bb_rgbd_encoder: workspace of %lld bytes < %lld", (long long)ws_bytes, rgbd_encoder_workspace_bytes(n));
+  if (train && index && n > 0) {
+    // a negative entry skips its row (eval mode only): batch statistics need every row.  The index is
+    // device memory, so this check reads it back -- outside a stream capture only (a captured
+    // train-mode call cannot be checked: non-negative entries are then the caller's contract)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
+      std::vector<long long> host(static_cast<size_t>(n));
+      HIPCHK(hipMemcpyAsync(host.data(), index, sizeof(long long) * size_t(n), hipMemcpyDeviceToHost,
+                            (hipStream_t)stream));
+      HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+      for (int64_t i = 0; i < n; i++)
+        if (host[size_t(i)] < 0)
+          return fail("bb_rgbd_encoder: index[%lld] = %lld is negative in train mode (a skipped row: eval mode only)",
+                      (long long)i, host[size_t(i)]);
+    }
+  }
+  EncArgs a{};
+  a.p = EncParams{p->conv1_w, p->conv1_b, p->bn1_w, p->bn1_b, p->bn1_mean, p->bn1_var,
+                  reinterpret_cast<long long*>(p->bn1_count), p->conv2_w, p->conv2_b, p->bn2_w, p->bn2_b,
+                  p->bn2_mean, p->bn2_var, reinterpret_cast<long long*>(p->bn2_count), p->fc_w, p->fc_b, p->bn3_w,
+                  p->bn3_b, p->bn3_mean, p->bn3_var, reinterpret_cast<long long*>(p->bn3_count)};
+  a.images = images; a.image_stride = image_stride; a.index = reinterpret_cast<const long long*>(index);
+  a.n = n; a.train = train ? 1 : 0;
+  a.momentum = momentum; a.eps = eps; a.out = out; a.out_stride = out_stride;
+  if (launch_rgbd_encoder(a, ws, (hipStream_t)stream))
+    return fail("bb_rgbd_encoder: launch failed: %s", hipGetErrorString(hipGetLastError()));
   return 0;
 }
 

@@ -35,6 +35,9 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--seed", type=int, default=10)
     ap.add_argument("--cameras", action="store_true", help="depth cameras on (rgbd policy branch)")
+    ap.add_argument("--rgbd", action="store_true",
+                    help="with --cameras: RGB-D frames (camera.disable_rgb: false); --frozen-encoder then pretrains "
+                         "a 4-channel encoder, which runs as bb_rgbd_encoder")
     ap.add_argument("--conv-benchmark", action="store_true", help="MIOpen kernel search for the CNN")
     ap.add_argument("--frozen-encoder", action="store_true",
                     help="with --cameras: pretrain a TinyAutoencoder on GPU frames first and freeze it (reference setup)")
@@ -61,21 +64,22 @@ def main():
     if a.log_reward_terms:
         log = {"reward_terms": True, "envs": list(range(min(a.log_reward_terms, a.envs))),
                "dir": str(Path(a.out) / "env_logs") if a.out else None}
+    cam_cfg = {"env_config": {"camera": {"disable_rgb": False}}} if a.cameras and a.rgbd else {}
     env = BallbotVecEnv(a.envs, device="cuda:0", precision=a.precision, seed=a.seed,
                         terrain_config={"type": a.terrain, "config": {}}, disable_cameras=not a.cameras,
-                        log_options=log)
+                        log_options=log, **cam_cfg)
     frozen, pre_s = None, 0.0
     if a.cameras and a.frozen_encoder:
-        from ballbot_rl.encoders import TinyAutoencoder, collect_depth_images, train_autoencoder
+        from ballbot_rl.encoders import TinyAutoencoder, collect_camera_images, train_autoencoder
 
         t = time.perf_counter()
         # frames from a separate env (>= 1024 envs: fast collection; the training env's terrain
         # streams stay untouched by the pretraining)
         penv = BallbotVecEnv(max(a.envs, 1024), device="cuda:0", precision=a.precision, seed=a.seed + 1,
-                             terrain_config={"type": a.terrain, "config": {}}, disable_cameras=False)
-        imgs = collect_depth_images(penv, 65536, seed=a.seed)
+                             terrain_config={"type": a.terrain, "config": {}}, disable_cameras=False, **cam_cfg)
+        imgs = collect_camera_images(penv, 65536, seed=a.seed)  # depth frames, or R, G, B, D with --rgbd
         penv.close()
-        ae = TinyAutoencoder(env.cam_h, env.cam_w)
+        ae = TinyAutoencoder(env.cam_h, env.cam_w, in_c=env.cam_channels)
         train_autoencoder(ae, imgs, epochs=2, batch_size=256, log=lambda *_: None)
         frozen = ae.encoder.eval()
         torch.cuda.synchronize()
@@ -118,7 +122,7 @@ def main():
 
         eenv = BallbotVecEnv(a.envs, device="cuda:0", precision=a.precision, seed=a.seed + a.envs,
                              stream_seeds=shard_stream_seeds(a.seed + a.envs, 0, a.envs),
-                             terrain_config={"type": a.terrain, "config": {}}, disable_cameras=not a.cameras)
+                             terrain_config={"type": a.terrain, "config": {}}, disable_cameras=not a.cameras, **cam_cfg)
         inner = EvalCallback(eenv, n_eval_episodes=a.eval_episodes, eval_freq=a.eval_freq, n_total_envs=a.envs,
                              log_path=Path(a.out) / "results" if a.out else None)
 
@@ -138,7 +142,7 @@ def main():
            "rollout_times_s": [round(x, 4) for x in roll_times], "update_times_s": [round(x, 4) for x in upd_times],
            "kl_stops": getattr(m, "kl_stops", None),
            "config": {"envs": a.envs, "n_steps": a.n_steps, "batch_size": a.batch, "n_epochs": a.epochs,
-                      "terrain": a.terrain, "precision": a.precision, "cameras": a.cameras,
+                      "terrain": a.terrain, "precision": a.precision, "cameras": a.cameras, "rgbd": bool(a.cameras and a.rgbd),
                       "frozen_encoder": frozen is not None, "encoder_pretrain_s": pre_s,
                       "log_reward_terms": a.log_reward_terms},
            "ep_rew_mean": _eprew(m), "ep_len_mean": _eplen(m), "env_stats": env.stats()}
